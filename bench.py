@@ -19,6 +19,13 @@ A rank whose WORLD_SIZE disagrees with ``--gpus`` exits with an error (never sil
 fewer GPUs than asked).
 
   python bench.py [--gpus N --steps K --warmup W --batch 4096 --dim 2048 --dtype bf16]
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the
+JSON line. ``--full`` adds the passes that take runs of their own (per-step HIP-event
+distribution, per-rank communication waits, the exact-fp32 secondary number); without it their
+fields are null. ``--dump-outputs DIR`` writes what the last timed step returned (loss, and the
+gradient w.r.t. the embeddings) as float32 ``DIR/<name>.npy``; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -42,6 +49,8 @@ import torch.distributed as dist  # noqa: E402
 METRIC = "NT-Xent fwd+bwd samples/sec, B=4096 d=2048, at 1/2/4/8 MI355X"
 BASELINE_VALUE = None  # BASELINE.json "published": {} — the reference publishes no numbers
 CHILD_ENV = "NTXENT_BENCH_RANK_CHILD"
+DUMP_MAX_BYTES = 32 * 10**6  # --dump-outputs: the gradient is row-sampled above this
+DUMP_SEED = 20240  # ... with this seed
 
 
 def parse(argv=None):
@@ -86,9 +95,17 @@ def parse(argv=None):
     ap.add_argument("--graph", action="store_true",
                     help="capture one full fwd+bwd step in a hipGraph (torch.cuda.CUDAGraph) and replay it "
                          "every step (1 GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beyond the headline figure: HIP events around each step "
+                         "(step_ms*), per-rank communication waits at N > 1 (comm_wait_*) and the exact-fp32 "
+                         "secondary number (see --secondary-fp32)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: after the timed steps write what the last of them returned as float32 "
+                         "DIR/loss.npy and DIR/grad.npy (a fixed, seeded sample of rows, in ascending row "
+                         "order, where the gradient exceeds %d MB)" % (DUMP_MAX_BYTES // 10**6))
     ap.add_argument("--secondary-fp32", default="auto", choices=["auto", "on", "off"],
-                    help="also time the exact-fp32 MFMA path (fp32 inputs, fp32 compute) at the same shape "
-                         "(auto: on for 1 GPU)")
+                    help="with --full: also time the exact-fp32 MFMA path (fp32 inputs, fp32 compute) at the "
+                         "same shape (auto: on for 1 GPU)")
     ap.add_argument("--prewarm-steps", type=int, default=60,
                     help="untimed steps run BEFORE the --warmup steps so the timed region measures the "
                          "steady state: from a cold start the GPU clock ramps for ~60 steps (0.51 ms/step "
@@ -360,11 +377,13 @@ def run_rank(a) -> None:
     # The timed region records no events at all, at every N (a timing event recorded between two
     # steps left a ~5-8 us bubble per step in the kernel trace, and the communication spans would
     # add several per step at N > 1): the per-step distribution and the per-rank communication
-    # waits come from a separate pass right after it.
+    # waits come from a separate pass right after it (--full).
     dt_s, _, _, loss, gh = timed(step, a.steps, a.warmup, per_step_events=False, comm=False)
     host_ms = timed.host_ms  # host CPU time to enqueue one step (autograd + launches) in the timed run
+    if a.dump_outputs and rank == 0:  # before any later pass steps again into the same buffers
+        dump_outputs(a.dump_outputs, loss, gh)
     per_ms = comm_ms = None
-    if on_gpu or world > 1:
+    if a.full and (on_gpu or world > 1):
         _, per_ms, comm_ms, _, _ = timed(step, min(a.steps, 20), 1, per_step_events=on_gpu, comm=world > 1)
     if a.host_profile and rank == 0:
         host_profile(step, a.host_profile, sync)
@@ -404,12 +423,13 @@ def run_rank(a) -> None:
     ms = dt_s / a.steps * 1e3
     value = world * a.batch / (ms / 1e3)
     comm_total = sum(comm_ms.values()) if comm_ms else 0.0
-    comm_all = rank_all(comm_total) if world > 1 else None
+    comm_all = rank_all(comm_total) if world > 1 and comm_ms is not None else None
     peak_all = rank_all(peak_mb) if peak_mb is not None and world > 1 else None
 
     secondary = None
-    want_fp32 = a.secondary_fp32 == "on" or (a.secondary_fp32 == "auto" and world == 1 and on_gpu
-                                             and a.impl == "fused" and a.dtype != "fp32" and not a.graph)
+    want_fp32 = a.full and (a.secondary_fp32 == "on" or (a.secondary_fp32 == "auto" and world == 1 and on_gpu
+                                                         and a.impl == "fused" and a.dtype != "fp32"
+                                                         and not a.graph))
     if want_fp32:
         del h, step, gh
         h32 = make_input(torch.float32)
@@ -435,6 +455,7 @@ def run_rank(a) -> None:
             "world_size_seen": world_seen,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": round(ms, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -528,6 +549,25 @@ def mfma_dtypes(a, world: int, rank: int, dev) -> dict:
     return {"forward": name.get(fwd, fwd), "backward": name.get(bwd, bwd)}
 
 
+def dump_outputs(path: str, loss, gh) -> None:
+    """What one step returns, as float32 .npy files: ``loss`` (0-d) and ``grad`` (rows, dim). A
+    gradient above DUMP_MAX_BYTES is cut to a sample of its rows drawn with DUMP_SEED (the same
+    rows, ascending, in every run of one shape)."""
+    import numpy as np
+
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    gh = gh.detach()
+    rows, row_bytes = gh.shape[0], 4 * gh[0].numel()
+    keep = max(1, DUMP_MAX_BYTES // row_bytes)
+    if keep < rows:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randperm(rows, generator=g)[:keep].sort().values
+        gh = gh.index_select(0, idx.to(gh.device))
+    np.save(out / "loss.npy", loss.detach().to("cpu", torch.float32).numpy())
+    np.save(out / "grad.npy", gh.to("cpu", torch.float32).contiguous().numpy())
+
+
 def host_profile(step, path: str, sync) -> None:
     """cProfile of the host side of 10 steps (the GPU runs behind); top entries by own time."""
     import cProfile
@@ -557,6 +597,8 @@ def main(argv=None):
     a = parse(argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1 (it is the number of timed steps)")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(launch(a, argv))  # launcher: no GPU access in this process
     run_rank(a)

@@ -62,7 +62,7 @@ def visible_gpus() -> int:
 def run_one(a, n: int) -> dict:
     cmd = [sys.executable, str(BENCH), "--gpus", str(n), "--steps", str(a.steps), "--warmup", str(a.warmup),
            "--batch", str(a.batch), "--dim", str(a.dim), "--negatives", a.negatives, "--device", a.device,
-           "--dtype", a.dtype, "--timeout", str(a.timeout), "--secondary-fp32", "off"]
+           "--dtype", a.dtype, "--timeout", str(a.timeout), "--full", "--secondary-fp32", "off"]  # comm_wait_*
     if a.backend:
         cmd += ["--backend", a.backend]
     if a.share_gpu:
