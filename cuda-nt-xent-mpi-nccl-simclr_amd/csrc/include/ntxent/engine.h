@@ -4,9 +4,10 @@
 // call (src/ntxent_kernel.cu:138-239). Engine is the MI355X-native replacement for C++
 // users, the native benchmark and the C++ tests:
 //
-//   * one arena allocation per (shape, dtype, world) sized up front — no allocation, host
-//     sync or host decision inside a step, so a whole fwd+bwd step is hipGraph-capturable
-//     (capture()/replay()) and replays with no per-kernel launch overhead;
+//   * one arena allocation per (shape, dtype, world) sized up front — no allocation or host
+//     sync inside a step, so a whole fwd+bwd step is hipGraph-capturable (capture()/replay())
+//     and replays with no per-kernel launch overhead; the step itself is the shared launch
+//     sequence of step.h (the symmetric mode has its own, engine_sym.cpp);
 //   * data parallel through a Comm (RCCL over xGMI): prep writes this rank's normalised rows
 //     straight into its slot of the gathered buffer, the all-gathers run on a high-priority
 //     comm stream while the own-rank (upper-triangular) tiles are computed, and only the
@@ -26,6 +27,7 @@
 
 #include "ntxent/comm.h"
 #include "ntxent/ntxent.h"
+#include "ntxent/step.h"
 
 namespace ntxent {
 
@@ -63,7 +65,7 @@ struct EngineConfig {
   int device = -1;            // -1: current device
 };
 
-class Engine {
+class Engine : private StepComm {
  public:
   explicit Engine(const EngineConfig& cfg, Comm* comm = nullptr);
   ~Engine();
@@ -88,7 +90,7 @@ class Engine {
 
   float loss(hipStream_t stream);  // synchronises `stream`
   const float* loss_device() const { return loss_; }
-  const float* lse2_device() const { return lse2_all_; }  // [W*Rpad], log2 units
+  const float* lse2_device() const { return lse2_all_; }  // [W*Rpad] (small path: small_rows_pad), log2 units
   const float* inv_norm_device() const { return inv_; }
   const Geometry& geometry() const { return g_; }
   const EngineConfig& config() const { return cfg_; }
@@ -96,7 +98,7 @@ class Engine {
   int fwd_tiles() const { return n_fwd_; }
   int own_tiles() const { return n_own_; }
   int dz_tiles() const { return n_dz_; }
-  bool small() const { return small_; }
+  bool small() const { return ov_.small_path == 1; }
   bool symmetric() const { return symm_; }
   Comm* comm() const { return comm_; }
 
@@ -109,9 +111,18 @@ class Engine {
   int n_fwd_ = 0, n_own_ = 0, n_dz_ = 0;
   size_t cs_ = 2;             // bytes per element of the backward dtype (zq, ZqT, cosines, C)
   bool f8_ = false;           // fp8 forward GEMM (e4m3 copy zq8_all_), fp16 backward
-  bool fuse_ = false;          // normalisation backward in the dZ epilogue (NormFuse)
+  // what the arena was sized for (small path, fp8 backward, small splits), frozen at construction;
+  // plan() resolves the rest per call, so the process-wide toggles take effect on the next step
+  StepOverrides ov_;
+  StepPlan plan() const { return resolve_step_plan(g_, cfg_.input, cfg_.compute, cfg_.keep_cos, ws_.num_cus, ov_); }
+  StepBuffers buffers(const float* grad_out, void* dh) const;
+  // the all-gather mode's communication between the step's launches (world > 1)
+  void after_prep(hipStream_t s) override;
+  void before_remote(hipStream_t s) override;
+  void after_lse(hipStream_t s) override;
+  void before_dz(hipStream_t s) override;
   int* dot_cnt_ = nullptr;     // dot fold counters (NormFuse::dot_cnt)
-  float* dotp_ = nullptr;      // dot partials [Rpad][dot_slots] (fuse_)
+  float* dotp_ = nullptr;      // dot partials [Rpad][dot_slots] (StepPlan::fuse)
   float* dot_ = nullptr;       // dot [Rpad]
   // symmetric data-parallel mode (Negatives::kSymmetric, engine_sym.cpp)
   bool symm_ = false;
@@ -138,11 +149,9 @@ class Engine {
   void dz_view(const char* abuf, long a_tile0, long a_panel_tiles, const char* bbuf, int b_block0, long b_col0,
                int k_tiles, int m0, int m1, void* out, bool accum, bool out_f16, hipStream_t s,
                const GemmWorkspace& ws);
-  bool q8_ = false;            // fp8 backward (e4m3 C and Z^T, EngineConfig::fp8_backward)
   float* q8_mneg_ = nullptr;   // Q8Stats: negatives-only row max [Rpad], min LSE [1]
   float* q8_lmin_ = nullptr;
   char* zq8t_ = nullptr;       // e4m3(256 Zq^T) [dim_n][q8_ldt]
-  bool small_ = false;        // small-problem path (small_kernels.hip)
   void* small_scratch_ = nullptr;
   DType bwd_ = DType::F16;
   void* arena_ = nullptr;

@@ -350,8 +350,9 @@ bool launch_dz(DType comp, const void* cbuf, const void* zqt_all, const int4* ti
                bool half_c = false);
 // Half C (SimParams::c_half): the coefficient pass writes the upper tiles only and the dZ stages a
 // lower K tile C_IJ (J < I) from C_JI through a transposing LDS image (ds_read_b64_tr_b16, one
-// lane base per wave). Needs a 16-bit backward, one rank and whole-tile dZ items (the schedule of
-// launch_dz: no split-K, no stream-K remainder). (Round 3's dz_sym also read Z through transposed
+// lane base per wave). Needs a 16-bit backward, one rank and dZ items that all start at an even
+// K-step (the schedule of launch_dz: whole tiles, or split-K pieces of an even number of K-steps as
+// at d = 512; not a stream-K remainder). (Round 3's dz_sym also read Z through transposed
 // LDS reads, 33 us slower at the headline, ~10 us of it the mirrored A K-steps: profiles/r3/dzexp.)
 bool dz_half_c_eligible(DType comp, const Geometry& g, int n_dz, const GemmWorkspace& ws);
 void set_half_c(bool on);  // default: NTXENT_HALF_C (unset: on)

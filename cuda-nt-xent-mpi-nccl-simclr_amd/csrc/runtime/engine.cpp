@@ -48,7 +48,6 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   if (f8_) cfg_.keep_cos = true;  // fp8: the fp16 backward uses the forward's own cosines
   bwd_ = backward_dtype(cfg.compute);
   cs_ = dtype_size(bwd_);
-  small_ = cfg.small_path && world_ == 1 && small_path_eligible(g_, cfg.compute);
   symm_ = world_ > 1 && cfg.negatives == Negatives::kSymmetric;
   if (symm_) {
     cfg_.keep_cos = true;  // the coefficient pass reads both blocks' cosines from the forward
@@ -57,44 +56,48 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
     nch_ = sym_num_chunks(g_.row_tiles);
     ccs_ = bwd_ == DType::F32 ? 4 : 2;
   }
-  q8_ = !small_ && fp8_backward_eligible(g_, cfg.compute) &&
-        (cfg.fp8_backward < 0 ? fp8_backward_enabled() : cfg.fp8_backward != 0);
-  // normalisation backward fused into the dZ epilogue (the coefficient pass emits dot partials;
-  // the symmetric mode sums received contributions in launch_norm_bwd instead)
-  // (not on fp8 plans: dot_i = sum_j C_ij cos_ij would use the e4m3 forward's cosines, ~1e-2 off)
-  fuse_ = !small_ && !symm_ && !f8_ && bwd_ != DType::F32 && g_.dim % 8 == 0;
+  ws_.num_cus = device_info(device_).num_cus;
+  ov_.small_path = cfg.small_path;
+  ov_.small_splits = std::max(0, cfg.small_splits);
+  ov_.fp8_backward = cfg.fp8_backward;
+  const StepPlan p = plan();
+  ov_.small_path = p.small;  // the arena below is sized for these two
+  ov_.fp8_backward = p.q8;
+  const StepBufferBytes nb = step_buffer_bytes(p);
 
   const auto ft = symm_ ? build_sym_fwd_tiles(g_, jobs_, nch_) : build_fwd_tiles(g_);
   const auto dt = build_dz_tiles(g_);
   n_fwd_ = (int)ft.size();
   n_own_ = count_own_fwd_tiles(g_);
   n_dz_ = (int)dt.size();
-  ws_.num_cus = device_info(device_).num_cus;
+  NTXENT_CHECK((symm_ || n_fwd_ == p.n_fwd) && n_own_ == p.n_own && n_dz_ == p.n_dz, "Engine: plan / tile list mismatch");
   ws_.bytes = gemm_workspace_bytes(std::max(n_fwd_, n_dz_), ws_.num_cus);
 
-  const size_t W = world_, Rp = g_.rows_pad, R = g_.rows;
+  const size_t Rp = g_.rows_pad;
   struct Slot { void** p; size_t bytes; };
+  // the symmetric mode (engine_sym.cpp) keeps its own cosine / coefficient / slab layouts and
+  // sums received contributions in launch_norm_bwd (no fused normalisation backward)
   const std::vector<Slot> slots = {
-      {(void**)&zq_all_, W * Rp * g_.ld_k * cs_},
-      {(void**)&zq8_all_, f8_ ? W * Rp * g_.ld_k8 : 0},
-      {(void**)&zqt_all_, q8_ ? 0 : W * g_.dim_n * g_.ld_t * cs_},
-      {(void**)&zq8t_, q8_ ? (size_t)g_.dim_n * (size_t)q8_ldt(g_) : 0},
-      {(void**)&q8_mneg_, q8_ ? Rp * 4 : 0},
-      {(void**)&q8_lmin_, q8_ ? (size_t)4 : (size_t)0},
-      {(void**)&inv_, R * 4},
-      {(void**)&ypos_, R * 4},
-      {(void**)&part_, (size_t)g_.col_tiles * Rp * sizeof(float2)},
-      {(void**)&sbuf_, cfg_.keep_cos ? (size_t)n_fwd_ * kTileElems * cs_ : 0},
-      {(void**)&cbuf_, (size_t)g_.row_tiles * (symm_ ? sym_c_ld(g_) : g_.col_tiles) * kTileElems * cs_},
-      {(void**)&lse2_all_, W * Rp * 4},
-      {(void**)&cpos_, Rp * 4},
-      {(void**)&block_loss_, (size_t)lse_scratch_floats(g_) * 4},
-      {(void**)&loss_, 4},
+      {(void**)&zq_all_, nb.zq},
+      {(void**)&zq8_all_, nb.zq8},
+      {(void**)&zqt_all_, nb.zqt},
+      {(void**)&zq8t_, nb.zq8t},
+      {(void**)&q8_mneg_, nb.q8_mneg},
+      {(void**)&q8_lmin_, nb.q8_lmin},
+      {(void**)&inv_, nb.inv},
+      {(void**)&ypos_, nb.ypos},
+      {(void**)&part_, nb.part},
+      {(void**)&sbuf_, symm_ ? (size_t)n_fwd_ * kTileElems * cs_ : nb.sbuf},
+      {(void**)&cbuf_, symm_ ? (size_t)g_.row_tiles * sym_c_ld(g_) * kTileElems * cs_ : nb.cbuf},
+      {(void**)&lse2_all_, nb.lse2},
+      {(void**)&cpos_, nb.cpos},
+      {(void**)&block_loss_, nb.block_loss},
+      {(void**)&loss_, nb.loss},
       {(void**)&one_, 4},
       // symmetric mode, fp32 plans: the received contributions follow the own slab (one stack)
-      {(void**)&slabs_, Rp * g_.dim_n * 4 * (symm_ && ccs_ == 4 ? 1 + inc_.size() : 1)},
-      {(void**)&fold_pre_, world_ == 1 ? Rp * sizeof(float2) : 0},
-      {(void**)&fold_cnt_, world_ == 1 ? (Rp / 64 + 1) * sizeof(int) : 0},
+      {(void**)&slabs_, symm_ ? Rp * g_.dim_n * 4 * (ccs_ == 4 ? 1 + inc_.size() : 1) : nb.slabs},
+      {(void**)&fold_pre_, nb.fold_pre},
+      {(void**)&fold_cnt_, nb.fold_cnt},
       {(void**)&part_x_, symm_ ? (size_t)g_.col_tiles * Rp * sizeof(float2) : 0},
       {(void**)&xsend_, symm_ ? sym_xpack_floats2(jobs_, g_.row_tiles) * sizeof(float2) : 0},
       {(void**)&xrecv_, symm_ ? sym_xpack_floats2(inc_, g_.row_tiles) * sizeof(float2) : 0},
@@ -102,13 +105,13 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
       {(void**)&contrib_, symm_ ? (jobs_.size() + 1) * Rp * g_.dim_n * ccs_ : 0},
       {(void**)&recv_, symm_ && ccs_ == 2 ? inc_.size() * Rp * g_.dim_n * ccs_ : 0},
       {(void**)&dz_rows_, symm_ ? (size_t)4 * (world_ + 1) * g_.row_tiles * (g_.dim_n / kTile) * sizeof(int4) : 0},
-      {(void**)&dotp_, fuse_ ? Rp * (size_t)dot_slots(g_) * 4 : 0},
-      {(void**)&dot_, fuse_ ? Rp * 4 : 0},
-      {(void**)&dot_cnt_, fuse_ ? 2 * sizeof(int) : 0},
+      {(void**)&dotp_, symm_ ? 0 : nb.dotp},
+      {(void**)&dot_, symm_ ? 0 : nb.dot},
+      {(void**)&dot_cnt_, symm_ ? 0 : nb.dot_cnt},
       {(void**)&fwd_tiles_, ft.size() * sizeof(int4)},
       {(void**)&dz_tiles_, dt.size() * sizeof(int4)},
       {&ws_.ptr, ws_.bytes},
-      {&small_scratch_, small_ ? small_scratch_bytes(g_, std::max(small_bwd_splits(g_), cfg.small_splits)) : 0},
+      {&small_scratch_, nb.small_scratch},
   };
   size_t total = 0;
   for (const auto& s : slots) total += align_up(s.bytes);
@@ -149,6 +152,39 @@ Engine::~Engine() {
   if (arena_) hipFree(arena_);
 }
 
+StepBuffers Engine::buffers(const float* grad_out, void* dh) const {
+  StepBuffers b;
+  b.h = h_;
+  b.zq = zq_all_;
+  b.zq8 = zq8_all_;
+  b.zqt = zqt_all_;
+  b.zq8t = zq8t_;
+  b.inv = inv_;
+  b.ypos = ypos_;
+  b.part = part_;
+  b.sbuf = sbuf_;
+  b.cbuf = cbuf_;
+  b.lse2 = lse2_all_;
+  b.cpos = cpos_;
+  b.q8_mneg = q8_mneg_;
+  b.q8_lmin = q8_lmin_;
+  b.block_loss = block_loss_;
+  b.loss = loss_;
+  b.fold_pre = fold_pre_;
+  b.fold_cnt = fold_cnt_;
+  b.dotp = dotp_;
+  b.dot = dot_;
+  b.dot_cnt = dot_cnt_;
+  b.slabs = slabs_;
+  b.fwd_tiles = fwd_tiles_;
+  b.dz_tiles = dz_tiles_;
+  b.small_scratch = small_scratch_;
+  b.grad_out = grad_out ? grad_out : one_;
+  b.dh = dh;
+  b.ws = ws_;
+  return b;
+}
+
 void Engine::forward(const void* h, hipStream_t s) {
   NTXENT_TRACE("ntxent.forward");
   h_ = h;
@@ -156,95 +192,10 @@ void Engine::forward(const void* h, hipStream_t s) {
     forward_sym(h, s);
     return;
   }
-  const size_t Rp = g_.rows_pad;
-  char* zq_local = zq_all_ + (size_t)rank_ * Rp * g_.ld_k * cs_;
-  char* zqt_local = zqt_all_ + (size_t)rank_ * g_.dim_n * g_.ld_t * cs_;
-  const bool raw = world_ == 1 && !small_ && !f8_ && cfg_.keep_cos && raw_forward_enabled() &&
-                   raw_forward_eligible(g_, cfg_.input, cfg_.compute);
-  RawRows rr;
-  rr.h = h;
-  rr.in = cfg_.input;
-  rr.inv = inv_;
-  rr.zqt = zqt_local;
-  rr.zt = bwd_;
-  // the LSE launch's outputs: the diagonal remainder's launch may compute them (rr.lse_folded)
-  rr.ypos = ypos_;
-  rr.lse2 = lse2_all_;
-  rr.cpos = cpos_;
-  rr.block_loss = block_loss_;
-  rr.loss = loss_;
-  rr.fold_pre = fold_pre_;
-  rr.fold_cnt = fold_cnt_;
-  // forward GEMM operand: the e4m3 rows for fp8 plans, else zq itself (or the input rows: raw)
-  char* op_all = f8_ ? zq8_all_ : zq_all_;
-  const size_t op_bytes = f8_ ? Rp * g_.ld_k8 : Rp * g_.ld_k * cs_;
-  char* op_local = op_all + (size_t)rank_ * op_bytes;
-  {
-    NTXENT_TRACE("ntxent.prep");
-    fault_point("prep");
-    if (small_) {  // one launch (row prologue fused up to kSmallFuseMaxRows): tiles + LSE merge + loss
-      // (lse2 -> lse2_all_, a_i -> cpos_)
-      if (!small_fwd_fused(g_)) launch_prep(cfg_.input, bwd_, h, zq_local, inv_, ypos_, g_, s);
-      NTXENT_TRACE("ntxent.small_fwd");
-      fault_point("fwd");
-      launch_small_fwd(cfg_.input, cfg_.compute, h, zq_local, inv_, ypos_, lse2_all_, cpos_, loss_, small_scratch_,
-                       g_, s);
-      if (fault_armed("nonfinite")) NTXENT_HIP_CHECK(hipMemsetAsync(loss_, 0xFF, 4, s));  // NaN
-      return;
-    }
-    // raw-operand forward (RawRows): no unit rows at all, the prologue computes inv and ypos only
-    launch_prep(cfg_.input, bwd_, h, raw ? nullptr : zq_local, inv_, ypos_, g_, s, f8_ ? op_local : nullptr);
-    // world 1: the transpose is written by the LSE launch (beside the merge, see below)
-    if (world_ > 1) launch_transpose(bwd_, zq_local, zqt_local, g_, s);
-  }
-  if (world_ > 1) {
-    // Gathers on the comm stream; the own-rank tiles only need this rank's slot.
-    NTXENT_HIP_CHECK(hipEventRecord(ev_prep_, s));
-    NTXENT_HIP_CHECK(hipStreamWaitEvent(comm_stream_, ev_prep_, 0));
-    comm_->all_gather(op_local, op_all, op_bytes, comm_stream_);
-    NTXENT_HIP_CHECK(hipEventRecord(ev_zq_, comm_stream_));
-    // the backward's B operand: the ZqT blocks
-    comm_->all_gather(zqt_local, zqt_all_, (size_t)g_.dim_n * g_.ld_t * cs_, comm_stream_);
-    NTXENT_HIP_CHECK(hipEventRecord(ev_zqt_, comm_stream_));
-    zqt_pending_ = true;
-  }
+  StepBuffers b = buffers(nullptr, nullptr);
   // both forward launches overlap a gather (rows, then ZqT): leave CUs for the RCCL kernels
-  bool zt_fwd = false;  // Z^T written by the forward launch (raw, beside the diagonal remainder)
-  GemmWorkspace ws_ovl = ws_;
-  if (world_ > 1) ws_ovl.sched_cus = std::max(1, ws_.num_cus - std::min(cfg_.comm_reserve_cus, ws_.num_cus / 2));
-  {
-    NTXENT_TRACE("ntxent.fwd_gemm.own");
-    fault_point("fwd");
-    zt_fwd = launch_fwd_stats(cfg_.compute, op_local, op_all, fwd_tiles_, n_own_, part_, sbuf_, ws_ovl, g_, s,
-                              BlockView{}, nullptr, own_diag_tail(g_), nullptr, raw ? &rr : nullptr);
-  }
-  if (n_fwd_ > n_own_) {
-    NTXENT_TRACE("ntxent.fwd_gemm.remote");
-    if (world_ > 1) NTXENT_HIP_CHECK(hipStreamWaitEvent(s, ev_zq_, 0));
-    launch_fwd_stats(cfg_.compute, op_local, op_all, fwd_tiles_ + n_own_, n_fwd_ - n_own_, part_,
-                     sbuf_ ? sbuf_ + (size_t)n_own_ * kTileElems * cs_ : nullptr, ws_ovl, g_, s);
-  }
-  fault_point("lse");
-  if (!(raw && rr.lse_folded)) {
-    NTXENT_TRACE("ntxent.lse");
-    if (q8_) {
-      Q8Stats q8;
-      q8.mneg2 = q8_mneg_;
-      q8.lmin = q8_lmin_;
-      q8.zq8t = zq8t_;
-      launch_lse(part_, ypos_, lse2_all_, cpos_, block_loss_, loss_, g_, s, bwd_, zq_local, nullptr, &q8);
-    } else if (world_ == 1)
-      launch_lse(part_, ypos_, lse2_all_, cpos_, block_loss_, loss_, g_, s, bwd_, raw ? nullptr : zq_local,
-                 zt_fwd ? nullptr : zqt_local, nullptr, raw && !zt_fwd ? &rr : nullptr);
-    else
-      launch_lse(part_, ypos_, lse2_all_, cpos_, block_loss_, loss_, g_, s);
-  }
-  if (world_ > 1) {
-    NTXENT_TRACE("ntxent.lse_gather");
-    comm_->all_gather(lse2_all_ + (size_t)rank_ * Rp, lse2_all_, Rp * 4, s);
-    comm_->all_reduce_sum(loss_, 1, s);
-  }
-  if (fault_armed("nonfinite")) NTXENT_HIP_CHECK(hipMemsetAsync(loss_, 0xFF, 4, s));  // NaN
+  if (world_ > 1) b.ws.sched_cus = std::max(1, ws_.num_cus - std::min(cfg_.comm_reserve_cus, ws_.num_cus / 2));
+  step_forward(plan(), b, s, world_ > 1 ? this : nullptr);
 }
 
 void Engine::backward(const float* grad_out, void* dh, hipStream_t s) {
@@ -254,67 +205,36 @@ void Engine::backward(const float* grad_out, void* dh, hipStream_t s) {
     backward_sym(grad_out, dh, s);
     return;
   }
-  const size_t Rp = g_.rows_pad;
-  const char* zq_local = zq_all_ + (size_t)rank_ * Rp * g_.ld_k * cs_;
-  Q8Stats q8;  // fp8 backward (q8_)
-  q8.mneg2 = q8_mneg_;
-  q8.lmin = q8_lmin_;
-  q8.zq = zq_local;
-  if (small_) {
-    NTXENT_TRACE("ntxent.small_bwd");
-    fault_point("dz");
-    launch_small_bwd(cfg_.input, cfg_.compute, zq_local, h_, inv_, lse2_all_, cpos_, grad_out ? grad_out : one_, dh,
-                     small_scratch_, g_, s, std::min(cfg_.small_splits, small_rows_pad(g_) / 64));
-    return;
-  }
-  // half C: upper coefficient tiles only, the dZ reads the lower ones transposed
-  const bool half_c = cfg_.keep_cos && !q8_ && half_c_enabled() && dz_half_c_eligible(bwd_, g_, n_dz_, ws_);
-  // the dot reduce folded into the dZ (NormFuse::dot_cnt)
-  const bool dfold = fuse_ && !q8_ && dz_dot_fold_eligible(bwd_, g_, n_dz_, ws_);
-  {
-    NTXENT_TRACE("ntxent.coef");
-    fault_point("coef");
-    if (cfg_.keep_cos)
-      launch_coef(bwd_, sbuf_, cbuf_, lse2_all_, cpos_, fwd_tiles_, n_fwd_, g_, s, nullptr, dotp_, q8_ ? &q8 : nullptr,
-                  half_c);
-    else
-      launch_coef_gemm(cfg_.compute, zq_local, zq_all_, cbuf_, lse2_all_, cpos_, fwd_tiles_, n_fwd_, ws_, g_, s,
-                       BlockView{}, dotp_);
-    if (fuse_ && !dfold) launch_dot_reduce(dotp_, dot_, g_, s);
-  }
-  if (zqt_pending_) {
-    NTXENT_HIP_CHECK(hipStreamWaitEvent(s, ev_zqt_, 0));
-    zqt_pending_ = false;
-  }
-  {
-    NTXENT_TRACE("ntxent.dz_gemm");
-    fault_point("dz");
-    NormFuse nf;
-    nf.h = h_;
-    nf.in = cfg_.input;
-    nf.inv = inv_;
-    nf.dot = dot_;
-    nf.grad_out = grad_out ? grad_out : one_;
-    nf.dh = dh;
-    if (dfold) {
-      nf.dotp = dotp_;
-      nf.dot_cnt = dot_cnt_;
-    }
-    const bool fused =
-        q8_ ? launch_dz(DType::FP8, cbuf_, zq8t_, dz_tiles_, n_dz_, slabs_, ws_, g_, s, /*out_f16=*/true,
-                        fuse_ ? &nf : nullptr, &q8, cpos_)
-            : launch_dz(bwd_, cbuf_, zqt_all_, dz_tiles_, n_dz_, slabs_, ws_, g_, s, /*out_f16=*/bwd_ != DType::F32,
-                        fuse_ ? &nf : nullptr, nullptr, nullptr, half_c);
-    if (fused) return;  // dh written by the dZ epilogue
-  }
-  {
-    NTXENT_TRACE("ntxent.norm_bwd");
-    fault_point("norm_bwd");
-    if (bwd_ != DType::F32)  // fp16 dZ slab (reduced-precision plans)
-      launch_norm_bwd(cfg_.input, nullptr, 0, h_, inv_, grad_out ? grad_out : one_, dh, g_, s, slabs_, 1);
-    else
-      launch_norm_bwd(cfg_.input, slabs_, 1, h_, inv_, grad_out ? grad_out : one_, dh, g_, s);
-  }
+  step_backward(plan(), buffers(grad_out, dh), s, world_ > 1 ? this : nullptr);
+}
+
+// Gathers on the comm stream; the own-rank tiles only need this rank's slot.
+void Engine::after_prep(hipStream_t s) {
+  char* op_all = f8_ ? zq8_all_ : zq_all_;
+  const size_t op_bytes = f8_ ? (size_t)g_.rows_pad * g_.ld_k8 : (size_t)g_.rows_pad * g_.ld_k * cs_;
+  const size_t zt_bytes = (size_t)g_.dim_n * g_.ld_t * cs_;
+  NTXENT_HIP_CHECK(hipEventRecord(ev_prep_, s));
+  NTXENT_HIP_CHECK(hipStreamWaitEvent(comm_stream_, ev_prep_, 0));
+  comm_->all_gather(op_all + (size_t)rank_ * op_bytes, op_all, op_bytes, comm_stream_);
+  NTXENT_HIP_CHECK(hipEventRecord(ev_zq_, comm_stream_));
+  // the backward's B operand: the ZqT blocks
+  comm_->all_gather(zqt_all_ + (size_t)rank_ * zt_bytes, zqt_all_, zt_bytes, comm_stream_);
+  NTXENT_HIP_CHECK(hipEventRecord(ev_zqt_, comm_stream_));
+  zqt_pending_ = true;
+}
+
+void Engine::before_remote(hipStream_t s) { NTXENT_HIP_CHECK(hipStreamWaitEvent(s, ev_zq_, 0)); }
+
+void Engine::after_lse(hipStream_t s) {
+  NTXENT_TRACE("ntxent.lse_gather");
+  comm_->all_gather(lse2_all_ + (size_t)rank_ * g_.rows_pad, lse2_all_, (size_t)g_.rows_pad * 4, s);
+  comm_->all_reduce_sum(loss_, 1, s);
+}
+
+void Engine::before_dz(hipStream_t s) {
+  if (!zqt_pending_) return;
+  NTXENT_HIP_CHECK(hipStreamWaitEvent(s, ev_zqt_, 0));
+  zqt_pending_ = false;
 }
 
 void Engine::capture(const void* h, void* dh, hipStream_t s) {

@@ -26,6 +26,7 @@
 
 #include "ntxent/engine.h"
 #include "ntxent/ntxent.h"
+#include "ntxent/step.h"
 
 namespace ntxent {
 namespace th {
@@ -114,7 +115,9 @@ std::shared_ptr<Plan> get_plan(int rows, int dim, int world, int rank, double te
   auto dt = build_dz_tiles(p->g);
   p->n_dz = (int)dt.size();
   p->dz_tiles = upload_tiles(dt, device);
-  p->small = small_path_eligible(p->g, comp);
+  StepOverrides small_on;  // eligibility, whatever set_small_path says
+  small_on.small_path = 1;
+  p->small = resolve_step_plan(p->g, DType::F16, comp, true, p->num_cus, small_on).small;
   cache.emplace(key, p);
   return p;
 }
@@ -295,32 +298,29 @@ at::Tensor lse(const at::Tensor& part, const at::Tensor& ypos, at::Tensor& lse2_
 }
 
 // Kept cosines (compact, one slot per forward tile) -> coefficient buffer (all tiles).
-at::Tensor coef(const at::Tensor& sbuf, const at::Tensor& lse2_all, const at::Tensor& cpos, const Plan& P,
-                float* dotp = nullptr, bool half_c = false) {
+at::Tensor coef(const at::Tensor& sbuf, const at::Tensor& lse2_all, const at::Tensor& cpos, const Plan& P) {
   check_input(sbuf, "sbuf");
   NTXENT_CHECK(sbuf.numel() == (long)P.n_fwd * kTileElems, "sbuf does not match the plan's forward tiles");
   const at::DeviceGuard guard(sbuf.device());
   auto cbuf = at::empty({(long)P.g.row_tiles * P.g.col_tiles * kTileElems}, sbuf.options());
   launch_coef(P.bwd(), sbuf.data_ptr(), cbuf.data_ptr(), lse2_all.data_ptr<float>(), cpos.data_ptr<float>(),
-              reinterpret_cast<const int4*>(P.fwd_tiles.data_ptr<int>()), P.n_fwd, P.g, cur_stream(sbuf), nullptr,
-              dotp, nullptr, half_c);
+              reinterpret_cast<const int4*>(P.fwd_tiles.data_ptr<int>()), P.n_fwd, P.g, cur_stream(sbuf));
   return cbuf;
 }
 
 at::Tensor coef_gemm(const at::Tensor& zq_local, const at::Tensor& zq_all, const at::Tensor& lse2_all,
-                     const at::Tensor& cpos, const Plan& P, float* dotp = nullptr) {
+                     const at::Tensor& cpos, const Plan& P) {
   check_input(zq_local, "zq_local");
   const at::DeviceGuard guard(zq_local.device());
   auto cbuf = at::empty({(long)P.g.row_tiles * P.g.col_tiles * kTileElems}, opts(zq_local, to_scalar(P.bwd())));
   auto ws = gemm_ws(zq_local, P.n_fwd, P);
   launch_coef_gemm(P.comp, zq_local.data_ptr(), zq_all.data_ptr(), cbuf.data_ptr(), lse2_all.data_ptr<float>(),
                    cpos.data_ptr<float>(), reinterpret_cast<const int4*>(P.fwd_tiles.data_ptr<int>()), P.n_fwd,
-                   ws, P.g, cur_stream(zq_local), BlockView{}, dotp);
+                   ws, P.g, cur_stream(zq_local));
   return cbuf;
 }
 
-at::Tensor dz(const at::Tensor& sc, const at::Tensor& zqt_all, const Plan& P, const NormFuse* nf = nullptr,
-              bool* fused = nullptr, bool half_c = false) {
+at::Tensor dz(const at::Tensor& sc, const at::Tensor& zqt_all, const Plan& P) {
   check_input(sc, "sc");
   check_input(zqt_all, "zqt_all");
   NTXENT_CHECK(zqt_all.numel() == (long)P.g.world * P.g.dim_n * P.g.ld_t, "zqt_all must be [world, dim_n, ld_t]");
@@ -329,10 +329,8 @@ at::Tensor dz(const at::Tensor& sc, const at::Tensor& zqt_all, const Plan& P, co
   const bool f16 = P.bwd() != DType::F32;
   auto slabs = at::empty({1, P.g.rows_pad, P.g.dim_n}, opts(sc, f16 ? at::kHalf : at::kFloat));
   auto ws = gemm_ws(sc, P.n_dz, P);
-  const bool f = launch_dz(P.bwd(), sc.data_ptr(), zqt_all.data_ptr(),
-                           reinterpret_cast<const int4*>(P.dz_tiles.data_ptr<int>()), P.n_dz, slabs.data_ptr(), ws, P.g,
-                           cur_stream(sc), f16, nf, nullptr, nullptr, half_c);
-  if (fused) *fused = f;
+  launch_dz(P.bwd(), sc.data_ptr(), zqt_all.data_ptr(), reinterpret_cast<const int4*>(P.dz_tiles.data_ptr<int>()),
+            P.n_dz, slabs.data_ptr(), ws, P.g, cur_stream(sc), f16);
   return slabs;
 }
 
@@ -572,20 +570,41 @@ at::Tensor norm_bwd_slabs(const at::Tensor& slabs, const at::Tensor& h, const at
 }
 
 // ---- single-process fused flows ------------------------------------------------------
-// Small-problem path (set_small_path, default on): the one-launch forward / backward of
-// small_kernels.hip for plans with Plan::small.
+// The step itself is step.cpp's (shared with the native Engine): these two resolve its plan,
+// allocate its buffers from torch's allocator (self-cleaning counters: the per-stream
+// device_scratch slots) and keep the tuple the autograd Function saves.
 
-static int small_splits(const Plan& P) {
-  const int nt = small_rows_pad(P.g) / 64;
-  const int o = small_splits_override();
-  return o > 0 ? std::min(o, nt) : small_bwd_splits(P.g);
+// at::empty of `bytes` in dtype t (ld > 0: rows of ld elements), its pointer stored in dst
+template <class T>
+static at::Tensor mk(T*& dst, const at::Tensor& like, size_t bytes, at::ScalarType t, long ld = 0) {
+  const long n = (long)(bytes / c10::elementSize(t));
+  at::Tensor x = ld > 0 ? at::empty({n / ld, ld}, opts(like, t)) : at::empty({n}, opts(like, t));
+  dst = static_cast<T*>(x.data_ptr());
+  return x;
 }
-static at::Tensor small_scratch(const at::Tensor& like, const Plan& P) {
-  return device_scratch(like, small_scratch_bytes(P.g, std::max(small_splits(P), small_bwd_splits(P.g))), 2);
+static void* scratch(const at::Tensor& like, size_t bytes, int slot) { return device_scratch(like, bytes, slot).data_ptr(); }
+
+static StepBuffers step_buffers(const at::Tensor& h, const Plan& P, const StepPlan& sp, const StepBufferBytes& nb) {
+  StepBuffers b;
+  b.h = h.data_ptr();
+  b.fwd_tiles = reinterpret_cast<const int4*>(P.fwd_tiles.data_ptr<int>());
+  b.dz_tiles = reinterpret_cast<const int4*>(P.dz_tiles.data_ptr<int>());
+  if (sp.small) {
+    b.small_scratch = scratch(h, nb.small_scratch, 2);
+  } else {
+    b.ws.num_cus = sp.num_cus;
+    b.ws.bytes = nb.ws;
+    b.ws.ptr = scratch(h, nb.ws, 0);
+  }
+  return b;
 }
 
-// Returns {loss, zq, zqt, inv, lse2, sc, cpos}; `sc` holds the kept cosines (keep_cos) or is
-// undefined.
+// Returns {loss, zq, zqt, inv, lse2, sc, cpos}, whose layout tells the backward what ran:
+//   small path: zqt undefined, cpos = a_i (the backward recomputes S from zq);
+//   raw-operand forward: zq empty (0 elements, the backward dtype: nothing reads unit rows);
+//   fp8 backward: zqt = e4m3(256 Zq^T) as uint8, cpos = [cpos | mneg2 (Rpad) | lmin] (Q8Stats);
+//   fp8 forward with the fp16 backward: 64 spare cpos entries (the backward sees fp16 rows);
+//   sc: the kept cosines (keep_cos; always on fp8 plans), else undefined.
 std::vector<at::Tensor> fused_forward(const at::Tensor& h, double T, const std::string& compute, bool keep_cos) {
   check_input(h, "h");
   NTXENT_CHECK(h.dim() == 2, "z must be 2-D [2N, d]");
@@ -594,101 +613,40 @@ std::vector<at::Tensor> fused_forward(const at::Tensor& h, double T, const std::
   // callers as an explicit "fp16".
   const DType comp = choose_compute(h.scalar_type(), false, compute);
   auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, T, dtype_name(comp), h.device().index());
-  if (P->small && small_path_enabled()) {
-    // {loss, zq, -, inv, lse2, -, a}: the backward recomputes S from zq (small_bwd). One launch:
-    // the forward kernel normalises the rows itself (small_fwd_fused) and writes zq / inv.
-    const int rp = small_rows_pad(P->g);
-    auto lse2 = at::empty({rp}, opts(h, at::kFloat));
-    auto arow = at::empty({rp}, opts(h, at::kFloat));
-    auto loss = at::empty({}, opts(h, at::kFloat));
-    at::Tensor zq, inv;
-    float* ypos = nullptr;
-    if (small_fwd_fused(P->g)) {
-      zq = at::empty({rp, P->g.ld_k}, opts(h, to_scalar(P->comp)));
-      inv = at::empty({P->g.rows}, opts(h, at::kFloat));
-    } else {
-      auto pr = prep(h, *P, c10::nullopt, c10::nullopt);
-      zq = pr[0];
-      inv = pr[1];
-      ypos = pr[2].data_ptr<float>();
+  const Geometry& g = P->g;
+  const StepPlan sp =
+      resolve_step_plan(g, to_dtype(h.scalar_type()), comp, keep_cos || comp == DType::FP8, P->num_cus);
+  const StepBufferBytes nb = step_buffer_bytes(sp);
+  const auto bt = to_scalar(sp.bwd);
+  StepBuffers b = step_buffers(h, *P, sp, nb);
+  at::Tensor zq8, zqt, ypos, part, sc, fold_pre;
+  auto inv = mk(b.inv, h, nb.inv, at::kFloat);
+  auto lse2 = mk(b.lse2, h, nb.lse2, at::kFloat);
+  auto loss = at::empty({}, opts(h, at::kFloat));
+  b.loss = loss.data_ptr<float>();
+  auto cpos = mk(b.cpos, h, nb.cpos + nb.q8_mneg + (sp.f8 ? 64 * 4 : 0), at::kFloat);
+  auto zq = sp.raw ? at::empty({0}, opts(h, bt)) : mk(b.zq, h, nb.zq, bt, g.ld_k);
+  if (!sp.small || !sp.small_fwd_fused) ypos = mk(b.ypos, h, nb.ypos, at::kFloat);
+  if (!sp.small) {
+    if (sp.raw) {
+      fold_pre = mk(b.fold_pre, h, nb.fold_pre, at::kFloat);
+      b.fold_cnt = static_cast<int*>(scratch(h, nb.fold_cnt, 3));
     }
-    launch_small_fwd(to_dtype(h.scalar_type()), P->comp, h.data_ptr(), zq.data_ptr(), inv.data_ptr<float>(), ypos,
-                     lse2.data_ptr<float>(), arow.data_ptr<float>(), loss.data_ptr<float>(),
-                     small_scratch(h, *P).data_ptr(), P->g, cur_stream(h));
-    return {loss, zq, at::Tensor(), inv, lse2, at::Tensor(), arow};
+    if (sp.f8) zq8 = mk(b.zq8, h, nb.zq8, at::kByte, g.ld_k8);
+    // ZqT (the dZ GEMM's B operand) is first read in the backward: the forward or the LSE launch
+    // writes it beside its own work (one stream: a side-stream transpose cost an event record and
+    // a join of ~5-7 us each, or stretched the forward GEMM when launched beside it).
+    zqt = sp.q8 ? mk(b.zq8t, h, nb.zq8t, at::kByte, q8_ldt(g)) : mk(b.zqt, h, nb.zqt, bt, g.ld_t);
+    part = mk(b.part, h, nb.part, at::kFloat);
+    if (sp.keep_cos) sc = mk(b.sbuf, h, nb.sbuf, bt);
+    if (sp.q8) {
+      b.q8_mneg = b.cpos + g.rows_pad;
+      b.q8_lmin = b.cpos + 2 * (size_t)g.rows_pad;
+    }
+    b.block_loss = static_cast<float*>(scratch(h, nb.block_loss, 1));
   }
-  const DType in = to_dtype(h.scalar_type());
-  if (keep_cos && comp != DType::FP8 && raw_forward_enabled() && raw_forward_eligible(P->g, in, comp)) {
-    // raw-operand forward (RawRows): the GEMM reads h itself and normalises in its epilogue; the
-    // prologue only computes inv and the positive logits, the LSE launch writes Z^T = (h inv)^T.
-    // zq is returned empty (0 elements, the backward dtype): nothing reads unit rows
-    auto inv = at::empty({P->g.rows}, opts(h, at::kFloat));
-    auto ypos = at::empty({P->g.rows}, opts(h, at::kFloat));
-    auto s = cur_stream(h);
-    launch_prep(in, P->bwd(), h.data_ptr(), nullptr, inv.data_ptr<float>(), ypos.data_ptr<float>(), P->g, s);
-    RawRows raw;
-    raw.h = h.data_ptr();
-    raw.in = in;
-    raw.inv = inv.data_ptr<float>();
-    auto zqt = at::empty({P->g.dim_n, P->g.ld_t}, opts(h, to_scalar(P->bwd())));
-    raw.zqt = zqt.data_ptr();
-    raw.zt = P->bwd();
-    auto part = at::empty({P->g.col_tiles, P->g.rows_pad, 2}, opts(h, at::kFloat));
-    auto sc = at::empty({(long)P->n_fwd * kTileElems}, opts(h, to_scalar(P->bwd())));
-    auto ws = gemm_ws(h, P->n_fwd, *P);
-    auto lse2 = at::empty({P->g.rows_pad}, opts(h, at::kFloat));
-    auto cpos = at::empty({P->g.rows_pad}, opts(h, at::kFloat));
-    auto block_loss = device_scratch(h, (size_t)lse_scratch_floats(P->g) * 4, 1);
-    auto loss = at::empty({}, opts(h, at::kFloat));
-    // the LSE outputs: the diagonal remainder's launch may compute them itself (RawRows::lse_folded)
-    raw.ypos = ypos.data_ptr<float>();
-    raw.lse2 = lse2.data_ptr<float>();
-    raw.cpos = cpos.data_ptr<float>();
-    raw.block_loss = static_cast<float*>(block_loss.data_ptr());
-    raw.loss = loss.data_ptr<float>();
-    auto fold_pre = at::empty({P->g.rows_pad, 2}, opts(h, at::kFloat));
-    raw.fold_pre = reinterpret_cast<float2*>(fold_pre.data_ptr<float>());
-    raw.fold_cnt = static_cast<int*>(device_scratch(h, (size_t)(P->g.rows_pad / 64 + 1) * 4, 3).data_ptr());
-    const bool zt_fwd = launch_fwd_stats(P->comp, nullptr, nullptr, reinterpret_cast<const int4*>(P->fwd_tiles.data_ptr<int>()), P->n_fwd,
-                     reinterpret_cast<float2*>(part.data_ptr<float>()), sc.data_ptr(), ws, P->g, s, BlockView{}, nullptr,
-                     P->n_fwd == P->n_own ? own_diag_tail(P->g) : 0, nullptr, &raw);
-    if (!raw.lse_folded)
-      launch_lse(reinterpret_cast<const float2*>(part.data_ptr<float>()), ypos.data_ptr<float>(), lse2.data_ptr<float>(),
-                 cpos.data_ptr<float>(), static_cast<float*>(block_loss.data_ptr()), loss.data_ptr<float>(), P->g, s,
-                 P->bwd(), nullptr, zt_fwd ? nullptr : zqt.data_ptr(), nullptr, zt_fwd ? nullptr : &raw);
-    return {loss, at::empty({0}, opts(h, to_scalar(P->bwd()))), zqt, inv, lse2, sc, cpos};
-  }
-  auto pr = prep(h, *P, c10::nullopt, c10::nullopt);
-  // ZqT (the dZ GEMM's B operand) is first read in the backward: the LSE launch writes it from
-  // extra blocks beside the merge (one stream: a side-stream transpose cost an event record and
-  // a join of ~5-7 us each, or stretched the forward GEMM when launched beside it).
-  auto zqt = at::empty({P->g.dim_n, P->g.ld_t}, pr[0].options());
-  // fp8 plans: the forward GEMM reads the e4m3 copy and always keeps its cosines (fp16), so
-  // the fp16 backward uses exactly the forward's logits
-  const bool f8 = comp == DType::FP8;
-  auto fs = f8 ? fwd_stats(pr[3], pr[3], *P, true) : fwd_stats(pr[0], pr[0], *P, keep_cos);
-  auto lse2 = at::empty({P->g.rows_pad}, opts(h, at::kFloat));
-  if (f8 && fp8_backward_enabled() && fp8_backward_eligible(P->g, comp)) {
-    // fp8 backward: zqt = e4m3(256 Zq^T) (uint8: the backward's marker); cpos carries the LSE
-    // pass's Q8Stats after its Rpad entries: [cpos | mneg2 (Rpad) | lmin]
-    const long Rp = P->g.rows_pad;
-    auto cpos = at::empty({2 * Rp + 64}, opts(h, at::kFloat));
-    auto zq8t = at::empty({P->g.dim_n, q8_ldt(P->g)}, opts(h, at::kByte));
-    Q8Stats q8;
-    q8.mneg2 = cpos.data_ptr<float>() + Rp;
-    q8.lmin = cpos.data_ptr<float>() + 2 * Rp;
-    q8.zq8t = zq8t.data_ptr();
-    auto block_loss = device_scratch(h, (size_t)lse_scratch_floats(P->g) * 4, 1);
-    auto loss = at::empty({}, opts(h, at::kFloat));
-    launch_lse(reinterpret_cast<const float2*>(fs[0].data_ptr<float>()), pr[2].data_ptr<float>(), lse2.data_ptr<float>(),
-               cpos.data_ptr<float>(), static_cast<float*>(block_loss.data_ptr()), loss.data_ptr<float>(), P->g,
-               cur_stream(h), DType::F16, pr[0].data_ptr(), nullptr, &q8);
-    return {loss, pr[0], zq8t, pr[1], lse2, fs[1], cpos};
-  }
-  // (fp8 plans: 64 spare entries mark the e4m3 forward for the backward, which sees the fp16 rows)
-  auto cpos = at::empty({P->g.rows_pad + (f8 ? 64 : 0)}, opts(h, at::kFloat));
-  auto loss = lse(fs[0], pr[2], lse2, cpos, *P, pr[0], zqt);
-  return {loss, pr[0], zqt, pr[1], lse2, fs[1], cpos};
+  step_forward(sp, b, cur_stream(h));
+  return {loss, zq, zqt, inv, lse2, sc, cpos};
 }
 
 at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::optional<at::Tensor>& zqt_in,
@@ -696,103 +654,53 @@ at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::
                           const at::Tensor& lse2, const c10::optional<at::Tensor>& sc_in, const at::Tensor& cpos,
                           const at::Tensor& grad_out, double T) {
   const at::DeviceGuard guard(h.device());
-  const DType comp = to_dtype(zq.scalar_type());
-  auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, T, dtype_name(comp), h.device().index());
+  const DType rows_dt = to_dtype(zq.scalar_type());
+  auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, T, dtype_name(rows_dt), h.device().index());
+  const Geometry& g = P->g;
   const at::Tensor zqt = zqt_in.has_value() ? *zqt_in : at::Tensor();
-  if (!zqt.defined()) {  // small-problem forward (see fused_forward): `cpos` holds a_i
-    NTXENT_CHECK(P->small, "fused_backward: missing ZqT for a large-problem plan");
-    auto go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
-    auto dh = at::empty_like(h);
-    launch_small_bwd(to_dtype(h.scalar_type()), P->comp, zq.data_ptr(), h.data_ptr(), inv.data_ptr<float>(),
-                     lse2.data_ptr<float>(), cpos.data_ptr<float>(), go.data_ptr<float>(), dh.data_ptr(),
-                     small_scratch(h, *P).data_ptr(), P->g, cur_stream(h), small_splits(*P));
-    return dh;
-  }
-  if (zqt.scalar_type() == at::kByte) {  // fp8 backward (see fused_forward)
-    const long Rp = P->g.rows_pad;
-    Q8Stats q8;
-    q8.mneg2 = const_cast<float*>(cpos.data_ptr<float>()) + Rp;
-    q8.lmin = const_cast<float*>(cpos.data_ptr<float>()) + 2 * Rp;
-    q8.zq = zq.data_ptr();
-    NTXENT_CHECK(sc_in.has_value() && sc_in->defined() && cpos.numel() == 2 * Rp + 64,
-                 "fused_backward (fp8): kept cosines and the forward's Q8Stats required");
-    // (no fused normalisation backward on fp8 plans: its dot_i = sum_j C_ij cos_ij would use the
-    // e4m3 forward's cosines instead of z_i . g_i, a ~1e-2 radial error in dh)
-    const bool fuse = false;
-    at::Tensor dotp, dot, dh, go;
-    if (fuse) {
-      dotp = at::empty({Rp * dot_slots(P->g)}, opts(h, at::kFloat));
-      dot = at::empty({Rp}, opts(h, at::kFloat));
-    }
-    auto cb = at::empty({(long)P->g.row_tiles * P->g.col_tiles * kTileElems}, opts(h, at::kByte));
-    launch_coef(DType::F16, sc_in->data_ptr(), cb.data_ptr(), lse2.data_ptr<float>(), cpos.data_ptr<float>(),
-                reinterpret_cast<const int4*>(P->fwd_tiles.data_ptr<int>()), P->n_fwd, P->g, cur_stream(h), nullptr,
-                fuse ? dotp.data_ptr<float>() : nullptr, &q8);
-    NormFuse nf;
-    if (fuse) {
-      launch_dot_reduce(dotp.data_ptr<float>(), dot.data_ptr<float>(), P->g, cur_stream(h));
-      go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
-      dh = at::empty_like(h);
-      nf.h = h.data_ptr();
-      nf.in = to_dtype(h.scalar_type());
-      nf.inv = inv.data_ptr<float>();
-      nf.dot = dot.data_ptr<float>();
-      nf.grad_out = go.data_ptr<float>();
-      nf.dh = dh.data_ptr();
-    }
-    auto slabs = at::empty({1, P->g.rows_pad, P->g.dim_n}, opts(h, at::kHalf));
-    auto ws = gemm_ws(h, P->n_dz, *P);
-    const bool fused = launch_dz(DType::FP8, cb.data_ptr(), zqt.data_ptr(),
-                                 reinterpret_cast<const int4*>(P->dz_tiles.data_ptr<int>()), P->n_dz, slabs.data_ptr(),
-                                 ws, P->g, cur_stream(h), /*out_f16=*/true, fuse ? &nf : nullptr, &q8,
-                                 cpos.data_ptr<float>());
-    return fused ? dh : norm_bwd(slabs, h, inv, grad_out, *P);
-  }
-  // 16-bit plans finish the normalisation backward in the dZ epilogue with dot_i = z_i . g_i =
-  // sum_j C_ij cos_ij from partials the coefficient pass emits (not on fp8-forward plans: that sum
-  // would use the e4m3 forward's cosines)
-  const bool f8_fwd = cpos.numel() != P->g.rows_pad;  // see fused_forward
-  const bool fuse = P->bwd() != DType::F32 && P->g.dim % 8 == 0 && !f8_fwd;
-  at::Tensor dotp, dot;
-  if (fuse) {
-    dotp = at::empty({(long)P->g.rows_pad * dot_slots(P->g)}, opts(h, at::kFloat));
-    dot = at::empty({P->g.rows_pad}, opts(h, at::kFloat));
-  }
-  float* dp = fuse ? dotp.data_ptr<float>() : nullptr;
-  at::Tensor cb;
-  // half C: upper coefficient tiles only, the dZ reads the lower ones transposed (whole-tile dZ)
-  const bool half_c = sc_in.has_value() && sc_in->defined() && half_c_enabled() &&
-                      dz_half_c_eligible(P->bwd(), P->g, P->n_dz, gemm_ws(h, P->n_dz, *P));
-  if (sc_in.has_value() && sc_in->defined()) {
-    cb = coef(*sc_in, lse2, cpos, *P, dp, half_c);
-  } else {
+  const at::Tensor sc = sc_in.has_value() ? *sc_in : at::Tensor();
+  // what the forward ran, read off the tuple's layout (see fused_forward)
+  const bool q8 = zqt.defined() && zqt.scalar_type() == at::kByte;
+  const bool f8 = zqt.defined() && cpos.numel() != g.rows_pad;
+  StepOverrides ov;
+  ov.small_path = !zqt.defined();
+  ov.fp8_backward = q8;
+  // (sc undefined: a second backward (retain_graph), which recomputes the cosines)
+  const StepPlan sp = resolve_step_plan(g, to_dtype(h.scalar_type()), f8 ? DType::FP8 : rows_dt, sc.defined(),
+                                        P->num_cus, ov);
+  NTXENT_CHECK(sp.small == !zqt.defined(), "fused_backward: missing ZqT for a large-problem plan");
+  NTXENT_CHECK(sp.q8 == q8 && (!q8 || cpos.numel() == 2 * (long)g.rows_pad + 64),
+               "fused_backward (fp8): kept cosines and the forward's Q8Stats required");
+  const StepBufferBytes nb = step_buffer_bytes(sp);
+  StepBuffers b = step_buffers(h, *P, sp, nb);
+  auto go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
+  auto dh = at::empty_like(h);
+  b.inv = static_cast<float*>(inv.data_ptr());
+  b.lse2 = static_cast<float*>(lse2.data_ptr());
+  b.cpos = static_cast<float*>(cpos.data_ptr());
+  at::Tensor zr = zq, cb, dotp, dot, slabs;
+  if (!sp.small) {
     // (a raw-operand forward returns no unit rows: a second backward rebuilds them to recompute S)
-    const at::Tensor zr = zq.numel() > 0 ? zq : prep(h, *P, c10::nullopt, c10::nullopt)[0];
-    cb = coef_gemm(zr, zr, lse2, cpos, *P, dp);
-  }
-  at::Tensor dh, go;
-  NormFuse nf;
-  // the dot reduce folded into the dZ (NormFuse::dot_cnt): per-stream counters (device_scratch)
-  const bool dfold = fuse && dz_dot_fold_eligible(P->bwd(), P->g, P->n_dz, gemm_ws(h, P->n_dz, *P));
-  if (fuse) {
-    if (dfold) {
-      nf.dotp = dp;
-      nf.dot_cnt = static_cast<int*>(device_scratch(h, 2 * sizeof(int), 4).data_ptr());
-    } else {
-      launch_dot_reduce(dp, dot.data_ptr<float>(), P->g, cur_stream(h));
+    if (!sp.keep_cos && zq.numel() == 0) zr = prep(h, *P, c10::nullopt, c10::nullopt)[0];
+    cb = mk(b.cbuf, h, nb.cbuf, sp.q8 ? at::kByte : to_scalar(sp.bwd));
+    slabs = mk(b.slabs, h, nb.slabs, sp.bwd != DType::F32 ? at::kHalf : at::kFloat);
+    if (sp.fuse) {
+      dotp = mk(b.dotp, h, nb.dotp, at::kFloat);
+      dot = mk(b.dot, h, nb.dot, at::kFloat);
     }
-    go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
-    dh = at::empty_like(h);
-    nf.h = h.data_ptr();
-    nf.in = to_dtype(h.scalar_type());
-    nf.inv = inv.data_ptr<float>();
-    nf.dot = dot.data_ptr<float>();
-    nf.grad_out = go.data_ptr<float>();
-    nf.dh = dh.data_ptr();
+    if (sp.dfold) b.dot_cnt = static_cast<int*>(scratch(h, nb.dot_cnt, 4));
+    (q8 ? b.zq8t : b.zqt) = zqt.data_ptr();
+    if (q8) {
+      b.q8_mneg = b.cpos + g.rows_pad;
+      b.q8_lmin = b.cpos + 2 * (size_t)g.rows_pad;
+    }
+    b.sbuf = sc.defined() ? sc.data_ptr() : nullptr;
   }
-  bool fused = false;
-  auto slabs = dz(cb, zqt, *P, fuse ? &nf : nullptr, &fused, half_c);
-  return fused ? dh : norm_bwd(slabs, h, inv, grad_out, *P);
+  b.zq = zr.data_ptr();
+  b.grad_out = go.data_ptr<float>();
+  b.dh = dh.data_ptr();
+  step_backward(sp, b, cur_stream(h));
+  return dh;
 }
 
 // ---- reference-compatible API (src/binding_new.cpp:5-20) -------------------------------
@@ -931,9 +839,6 @@ DType parse_dtype_name(const std::string& s) {
   if (s == "fp8" || s == "e4m3") return DType::FP8;
   throw std::invalid_argument("unknown dtype '" + s + "' (fp32|fp16|bf16|fp8)");
 }
-at::ScalarType scalar_of(DType t) {
-  return t == DType::F32 ? at::kFloat : (t == DType::F16 ? at::kHalf : at::kBFloat16);
-}
 
 class NativeEngine {
  public:
@@ -961,7 +866,7 @@ class NativeEngine {
     cfg.comm_reserve_cus = comm_reserve_cus;
     cfg.negatives = negatives == "symmetric" ? Negatives::kSymmetric : Negatives::kAllGather;
     cfg.device = device;
-    in_ = scalar_of(cfg.input);
+    in_ = to_scalar(cfg.input);
     eng_ = std::make_unique<Engine>(cfg, comm_.get());
   }
 
@@ -1138,12 +1043,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("zq_local"), py::arg("zq_all"), py::arg("plan"), py::arg("keep_cos"));
   m.def("lse", &lse, py::arg("part"), py::arg("ypos"), py::arg("lse2_all"), py::arg("cpos"), py::arg("plan"),
         py::arg("zq") = py::none(), py::arg("zqt") = py::none());
-  m.def("coef", [](const at::Tensor& sbuf, const at::Tensor& lse2_all, const at::Tensor& cpos, const Plan& P) {
-    return coef(sbuf, lse2_all, cpos, P);
-  }, py::arg("sbuf"), py::arg("lse2_all"), py::arg("cpos"), py::arg("plan"));
-  m.def("coef_gemm", [](const at::Tensor& zl, const at::Tensor& za, const at::Tensor& lse2_all, const at::Tensor& cpos,
-                        const Plan& P) { return coef_gemm(zl, za, lse2_all, cpos, P); });
-  m.def("dz", [](const at::Tensor& sc, const at::Tensor& zqt_all, const Plan& P) { return dz(sc, zqt_all, P); });
+  m.def("coef", &coef, py::arg("sbuf"), py::arg("lse2_all"), py::arg("cpos"), py::arg("plan"));
+  m.def("coef_gemm", &coef_gemm);
+  m.def("dz", &dz);
   m.def("set_fp8_backward", &ntxent::set_fp8_backward, py::arg("on"));
   m.def("set_raw_forward", &ntxent::set_raw_forward, py::arg("on"));
   m.def("raw_forward_enabled", &ntxent::raw_forward_enabled);
@@ -1238,6 +1140,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return r;
   }, py::arg("ntiles"), py::arg("nk"), py::arg("num_cus"));
   m.def("gemm_workspace_bytes", &ntxent::gemm_workspace_bytes);
+  // the decisions of the one-GPU step (step.h), as the autograd op and the Engine resolve them
+  m.def("step_plan", [](int rows, int dim, const std::string& input, const std::string& compute, bool keep_cos,
+                        int num_cus) {
+    const ntxent::DType comp = parse_dtype_name(compute);
+    const auto p = ntxent::resolve_step_plan(ntxent::make_geometry(rows, dim, 1, 0, 0.07f), parse_dtype_name(input),
+                                             comp, keep_cos || comp == ntxent::DType::FP8, num_cus);
+    py::dict r;
+    r["small"] = p.small; r["small_fwd_fused"] = p.small_fwd_fused; r["small_splits"] = p.small_splits;
+    r["f8"] = p.f8; r["q8"] = p.q8; r["raw"] = p.raw; r["fuse"] = p.fuse; r["half_c"] = p.half_c;
+    r["dfold"] = p.dfold; r["keep_cos"] = p.keep_cos; r["bwd"] = ntxent::dtype_name(p.bwd);
+    r["n_fwd"] = p.n_fwd; r["n_own"] = p.n_own; r["n_dz"] = p.n_dz;
+    r["forward_mfma"] = ntxent::dtype_name(p.fwd_mfma); r["backward_mfma"] = ntxent::dtype_name(p.bwd_mfma);
+    return r;
+  }, py::arg("rows"), py::arg("dim"), py::arg("input"), py::arg("compute"), py::arg("keep_cos") = true,
+     py::arg("num_cus") = 256);
   m.attr("TILE") = ntxent::kTile;
   m.attr("K_STEP_BYTES") = ntxent::kKStepBytes;
 }

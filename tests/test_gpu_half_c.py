@@ -3,9 +3,10 @@ lower K tile C_IJ (J < I) from C_JI through a transposing LDS image (SimParams::
 sim_gemm.h read_a_tr). The mirrored C holds the same values as C_JI^T, bit for bit, and the dZ
 accumulates in the same K order, so the gradient must be BITWISE the full-C gradient; and both
 within the usual tolerance of an fp64 oracle. Shapes: the headline (32 row panels), config 4 (8
-row panels, d = 8192), config 5 (64 row panels); config 2 (d = 512: split-K dZ) is not eligible
-and must fall back to the full C. Reference intent: /root/reference/src/ntxent_kernel.cu:232-262
-(the backward's gradient).
+row panels, d = 8192), config 5 (64 row panels) and config 2 (d = 512: a split-K dZ whose pieces
+start at even K-steps, so it takes half C as well). tests/test_planning.py asserts that every one
+of them takes half C (step_plan). Reference intent: the backward's gradient of the reference's
+src/ntxent_kernel.cu:232-262.
 """
 import pytest
 import torch

@@ -155,3 +155,96 @@ def test_superblock_order_covers_same_tiles_with_fewer_panels(C, rows):
         assert pa < pb - (1.5 if rt == 32 else 0.0), (pa, pb)
     else:
         assert a == b
+
+
+# ---- the one-GPU step's decisions (csrc/runtime/step.cpp, resolve_step_plan) ----------------
+# Expected values: what the parent commit's own eligibility functions and tile builders return
+# for each shape on 256 CUs with every toggle at its default (read off a host-only program linked
+# against them, not reasoned out). Keys left out of a row are not pinned for that shape.
+_LARGE = dict(small=False, small_fwd_fused=False, f8=False, q8=False, raw=True, fuse=True, half_c=True, dfold=True,
+              keep_cos=True, bwd="fp16", forward_mfma="bf16", backward_mfma="fp16")
+STEP_PLANS = {
+    "headline": ((8192, 2048, "bf16", "fp16"), dict(_LARGE, n_fwd=528, n_own=528, n_dz=256)),
+    "config2": ((8192, 512, "bf16", "fp16"), dict(_LARGE, n_fwd=528, n_own=528, n_dz=64)),
+    "config4": ((2048, 8192, "bf16", "fp16"), dict(_LARGE, n_fwd=36, n_own=36, n_dz=256)),
+    "config5-fp16": ((16384, 1024, "bf16", "fp16"), dict(_LARGE, n_fwd=2080, n_own=2080, n_dz=256)),
+    "config5-fp8": ((16384, 1024, "bf16", "fp8"),
+                    dict(_LARGE, f8=True, q8=True, raw=False, fuse=False, half_c=False, dfold=False,
+                         forward_mfma="fp8", backward_mfma="fp8", n_fwd=2080, n_own=2080, n_dz=256)),
+    "small-fused": ((512, 128, "bf16", "fp16"),
+                    dict(small=True, small_fwd_fused=True, small_splits=8, f8=False, q8=False, raw=False, fuse=False,
+                         half_c=False, dfold=False, bwd="fp16", forward_mfma="fp16", backward_mfma="fp16")),
+    "small-prep": ((2048, 128, "bf16", "fp16"),
+                   dict(small=True, small_fwd_fused=False, small_splits=8, raw=False, half_c=False, dfold=False)),
+    "fp32": ((2048, 256, "fp32", "fp32"),
+             dict(small=False, f8=False, q8=False, raw=False, fuse=False, half_c=False, dfold=False, bwd="fp32",
+                  forward_mfma="fp32", backward_mfma="fp32", n_fwd=36, n_own=36, n_dz=8)),
+    "dim-not-multiple-of-8": ((2500, 300, "bf16", "fp16"),
+                              dict(small=False, f8=False, q8=False, raw=False, fuse=False, half_c=True, dfold=False,
+                                   bwd="fp16", forward_mfma="fp16", backward_mfma="fp16", n_fwd=55, n_own=55,
+                                   n_dz=20)),
+}
+
+
+@pytest.mark.parametrize("name", list(STEP_PLANS))
+def test_step_plan_pins_the_decisions(C, name):
+    (rows, dim, inp, comp), want = STEP_PLANS[name]
+    plan = C.step_plan(rows, dim, inp, comp)
+    assert {k: plan[k] for k in want} == want
+
+
+def test_step_plan_follows_keep_cos_and_the_toggles(C):
+    # recompute: no kept cosines, so neither the raw-operand forward nor half C
+    plan = C.step_plan(8192, 2048, "bf16", "fp16", keep_cos=False)
+    assert not plan["keep_cos"] and not plan["raw"] and not plan["half_c"] and plan["fuse"] and plan["dfold"]
+    assert plan["forward_mfma"] == "fp16"
+    # fp8 plans always keep their cosines
+    assert C.step_plan(16384, 1024, "bf16", "fp8", keep_cos=False)["keep_cos"]
+    # resolved per call: a toggle flipped between two calls shows in the next plan
+    for get, put, key, args in [(C.half_c_enabled, C.set_half_c, "half_c", (8192, 2048, "bf16", "fp16")),
+                                (C.raw_forward_enabled, C.set_raw_forward, "raw", (8192, 2048, "bf16", "fp16")),
+                                (C.dot_fold_enabled, C.set_dot_fold, "dfold", (8192, 2048, "bf16", "fp16")),
+                                (C.fp8_backward_enabled, C.set_fp8_backward, "q8", (16384, 1024, "bf16", "fp8")),
+                                (C.small_path_enabled, C.set_small_path, "small", (512, 128, "bf16", "fp16"))]:
+        old = get()
+        try:
+            put(False)
+            assert not C.step_plan(*args)[key]
+            put(True)
+            assert C.step_plan(*args)[key]
+        finally:
+            put(old)
+
+
+@pytest.mark.parametrize("rows,dim", [(8192, 2048), (2048, 8192), (16384, 1024), (8192, 512)])
+def test_half_c_taken_at_every_shape_of_the_bitwise_test(C, rows, dim):
+    """tests/test_gpu_half_c.py::test_half_c_gradient_bitwise_equal_to_full_c compares half C against
+    the full C at these shapes; all four take half C, config 2's split-K dZ included (its pieces
+    start at even K-steps: dz_half_c_eligible)."""
+    assert C.step_plan(rows, dim, "bf16", "fp16")["half_c"]
+
+
+@pytest.mark.parametrize("name", list(STEP_PLANS))
+def test_bench_mfma_dtypes_agree_with_step_plan(C, monkeypatch, name):
+    """bench.py labels its JSON with its own copy of the raw-forward / fp8-backward rules
+    (mfma_dtypes). Run that code over a stand-in for the device-bound get_plan and compare with
+    the dtypes the step actually resolves."""
+    import argparse
+    import types
+
+    import torch
+
+    import bench
+    from ntxent_amd.ops import _ext
+
+    (rows, dim, inp, comp), _ = STEP_PLANS[name]
+    plan = C.step_plan(rows, dim, inp, comp)
+    shim = types.SimpleNamespace(
+        get_plan=lambda *a: types.SimpleNamespace(small=plan["small"], compute_dtype=comp, backward_dtype=plan["bwd"]),
+        raw_forward_enabled=C.raw_forward_enabled, fp8_backward_enabled=C.fp8_backward_enabled)
+    monkeypatch.setattr(_ext, "load", lambda *a, **k: shim)
+    a = argparse.Namespace(dtype=inp, compute=comp, impl="fused", batch=rows // 2, dim=dim, temperature=0.07,
+                           recompute=False)
+    got = bench.mfma_dtypes(a, 1, 0, torch.device("cuda", 0))
+    short = {k: v.split()[0].replace("e4m3", "fp8") for k, v in got.items()}
+    assert short == {"forward": plan["forward_mfma"], "backward": plan["backward_mfma"]}
