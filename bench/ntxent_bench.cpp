@@ -144,7 +144,8 @@ void* upload(std::vector<float>& host, DType in) {
 class Bench {
  public:
   Bench(int batch, int dim, DType in, DType comp, float T, bool keep_cos, Comm* comm, unsigned seed,
-        bool small_path = true, int small_splits = 0, Negatives neg = Negatives::kSymmetric)
+        bool small_path = true, int small_splits = 0, Negatives neg = Negatives::kSymmetric,
+        bool temperature_grad = false)
       : in_(in) {
     EngineConfig c;
     c.negatives = neg;
@@ -156,6 +157,7 @@ class Bench {
     c.keep_cos = keep_cos;
     c.small_path = small_path;
     c.small_splits = small_splits;
+    c.temperature_grad = temperature_grad;
     host_ = synthetic_views(c.rows, dim, seed);
     h_ = upload(host_, in);
     NTXENT_HIP_CHECK(hipMalloc(&dh_, host_.size() * dtype_size(in)));
@@ -232,6 +234,7 @@ class Bench {
   }
 
   float loss() { return e_->loss(s_); }
+  float temperature_grad() { return e_->temperature_grad(s_); }
 
   // host fp64 NT-Xent of the same inputs (small shapes, world 1 only)
   double host_loss() const {
@@ -293,6 +296,7 @@ struct Options {
   std::string dtype = "bf16", compute = "auto", json;
   float T = 0.07f;
   bool check = false, graph = false, recompute = false, small = true, grad_digest = false;
+  bool temperature_grad = false;  // world 1: the step also produces dL/dtau (one more small launch)
   int small_splits = 0;
   Negatives negatives = Negatives::kSymmetric;
   bool emulate = false;  // --gpus N as N emulated ranks on GPU 0 (ThreadComm), not N GPUs over RCCL
@@ -423,6 +427,7 @@ int main(int argc, char** argv) {
     else if (a == "--graph") o.graph = true;
     else if (a == "--recompute") o.recompute = true;
     else if (a == "--no-small") o.small = false;
+    else if (a == "--temperature-grad") o.temperature_grad = true;
     else if (a == "--fp8-bwd") ntxent::set_fp8_backward(true);
     else if (a == "--no-fp8-bwd") ntxent::set_fp8_backward(false);
     else if (a == "--no-raw-fwd") ntxent::set_raw_forward(false);
@@ -448,6 +453,7 @@ int main(int argc, char** argv) {
                   "  --fp8-bwd / --no-fp8-bwd: with --compute fp8, the backward's C and Z^T in e4m3 too (or fp16)\n"
                   "  --no-raw-fwd: unit-row (zq) forward operands instead of the input rows normalised in the epilogue\n"
                   "  --small-fuse-rows R: small forward with the row prologue fused up to R rows (0: prep launch)\n"
+                  "  --temperature-grad: time the step with the temperature gradient on (one GPU; prints dL/dtau)\n"
                   "  --grad-digest: print a hash of dh after one step (build variants must match bitwise)\n"
                   "  (the measured A/B alternatives of earlier rounds are deleted; build-time variants:\n"
                   "   tools/build_variant.sh)\n");
@@ -461,6 +467,7 @@ int main(int argc, char** argv) {
               check_matrix_core_support(dev) ? "yes (gfx950 MFMA)" : "no");
   const DType in = parse_dtype(o.dtype);
   const DType comp = o.compute == "auto" ? (in == DType::F32 ? DType::F32 : DType::F16) : parse_dtype(o.compute);
+  NTXENT_CHECK(!o.temperature_grad || o.gpus == 1, "--temperature-grad: one GPU only");
   if (o.gpus > 1) {
     if (o.batch <= 0) o.batch = 4096;
     if (o.dim <= 0) o.dim = 2048;
@@ -482,7 +489,8 @@ int main(int argc, char** argv) {
   if (jf) std::fprintf(jf, "{\"device\": \"%s\", \"results\": {", di.arch.c_str());
   bool first = true;
   for (auto [b, d] : shapes) {
-    Bench bench(b, d, in, comp, o.T, !o.recompute, nullptr, 1234, o.small, o.small_splits);
+    Bench bench(b, d, in, comp, o.T, !o.recompute, nullptr, 1234, o.small, o.small_splits, Negatives::kSymmetric,
+                o.temperature_grad);
     const char* path = bench.engine().small() ? "small" : "large";
     const Result f = stats(bench.time(0, o.warmup, o.iters));
     const Result bw = stats(bench.time(1, o.warmup, o.iters));
@@ -502,6 +510,7 @@ int main(int argc, char** argv) {
                    bench.engine().device_bytes());
       first = false;
     }
+    if (o.temperature_grad) std::printf("       temperature grad: dL/dtau %.9e\n", bench.temperature_grad());
     if (o.grad_digest) {
       const auto gd = bench.grad_digest();
       std::printf("       grad digest: %016llx l1 %.9e loss %.6f\n", gd.first, gd.second, bench.loss());

@@ -63,6 +63,10 @@ struct EngineConfig {
   int comm_reserve_cus = 8;
   Negatives negatives = Negatives::kSymmetric;  // world > 1 (kSymmetric keeps cosines)
   int device = -1;            // -1: current device
+  // world 1: backward() also produces dL/dtau (times grad_out): temperature_grad_device() /
+  // temperature_grad(). The arena then holds dtau and the per-row dot on every plan, and the step
+  // ends with one more small launch (launch_tau_grad), captured graphs included.
+  bool temperature_grad = false;
 };
 
 class Engine : private StepComm {
@@ -87,6 +91,14 @@ class Engine : private StepComm {
   void capture(const void* h, void* dh, hipStream_t stream);
   void replay(hipStream_t stream);
   bool captured() const { return exec_ != nullptr; }
+
+  // World 1: the following forward() / backward() run at `temperature`; nothing is reallocated
+  // (no buffer size or tile list depends on it). Drops a captured graph, whose kernel arguments
+  // hold the old value: captured() is false afterwards. Throws at world > 1.
+  void set_temperature(float temperature);
+  // EngineConfig::temperature_grad: dL/dtau of the last backward() (null without the option)
+  const float* temperature_grad_device() const { return dtau_; }
+  float temperature_grad(hipStream_t stream);  // synchronises `stream`
 
   float loss(hipStream_t stream);  // synchronises `stream`
   const float* loss_device() const { return loss_; }
@@ -114,7 +126,11 @@ class Engine : private StepComm {
   // what the arena was sized for (small path, fp8 backward, small splits), frozen at construction;
   // plan() resolves the rest per call, so the process-wide toggles take effect on the next step
   StepOverrides ov_;
-  StepPlan plan() const { return resolve_step_plan(g_, cfg_.input, cfg_.compute, cfg_.keep_cos, ws_.num_cus, ov_); }
+  StepPlan plan() const {
+    StepPlan p = resolve_step_plan(g_, cfg_.input, cfg_.compute, cfg_.keep_cos, ws_.num_cus, ov_);
+    p.tau_grad = cfg_.temperature_grad;
+    return p;
+  }
   StepBuffers buffers(const float* grad_out, void* dh) const;
   // the all-gather mode's communication between the step's launches (world > 1)
   void after_prep(hipStream_t s) override;
@@ -124,6 +140,7 @@ class Engine : private StepComm {
   int* dot_cnt_ = nullptr;     // dot fold counters (NormFuse::dot_cnt)
   float* dotp_ = nullptr;      // dot partials [Rpad][dot_slots] (StepPlan::fuse)
   float* dot_ = nullptr;       // dot [Rpad]
+  float* dtau_ = nullptr;      // dL/dtau [1] (EngineConfig::temperature_grad)
   // symmetric data-parallel mode (Negatives::kSymmetric, engine_sym.cpp)
   bool symm_ = false;
   std::vector<SymJob> jobs_, inc_;

@@ -378,9 +378,19 @@ void launch_dz_view(DType comp, const void* a, long long a_panel_tiles, const vo
 // xslabs (optional): nx more fp16 slabs [nx][Rpad][dim_n] added to the sum (received partner
 // contributions of the symmetric data-parallel mode, or the fp16 dZ of a reduced-precision plan
 // and nslabs = 0 fp32 slabs).
+// dot_out (optional, [rows]): also store each row's z_i . g_i (launch_tau_grad's input); dh is
+// bitwise the same with or without it.
 void launch_norm_bwd(DType in, const float* slabs, int nslabs, const void* h,
                      const float* inv, const float* grad_out, void* dh, const Geometry& g,
-                     hipStream_t stream, const void* xslabs = nullptr, int nx = 0);
+                     hipStream_t stream, const void* xslabs = nullptr, int nx = 0, float* dot_out = nullptr);
+
+// Temperature gradient of the loss (one rank):
+//   dtau[0] = -grad_out[0] * (sum over i < g.rows of dot[i]) / (2 * g.global_rows * tau^2)
+// with dot_i = sum_j C_ij cos_ij = z_i . g_i, the scalar of the normalisation backward: the reduced
+// dot of the fused dZ epilogue (NormFuse::dot, complete once the dZ launch has finished), or the
+// dot_out of launch_norm_bwd / launch_small_bwd. Rows at or beyond g.rows are not read. One block,
+// a fixed assignment of rows to threads and a fixed-order tree (fp64): deterministic, no atomics.
+void launch_tau_grad(const float* dot, const float* grad_out, float* dtau, const Geometry& g, hipStream_t stream);
 
 // ---- small-problem path (kernels/small_kernels.hip) -------------------------------------
 // Single-rank problems with R <= kSmallMaxRows and dim_k <= kSmallMaxDk in fp16/bf16: ONE
@@ -408,7 +418,9 @@ void launch_small_fwd(DType in, DType comp, const void* h, void* zq, float* inv,
 // splits <= 0: small_bwd_splits(g). grad_out: device fp32 scalar.
 void launch_small_bwd(DType in, DType comp, const void* zq, const void* h, const float* inv, const float* lse2,
                       const float* arow, const float* grad_out, void* dh, void* scratch, const Geometry& g,
-                      hipStream_t stream, int splits = 0);
+                      hipStream_t stream, int splits = 0, float* dot_out = nullptr);
+// dot_out (optional, [R]): each row's z_i . g_i, stored by the block that runs the row's epilogue
+// (with column splits: the last arriver).
 
 // ---- device utilities (reference utils::get_optimal_block_size / check_tensor_core_support
 //      at include/ntxent_kernel.cuh:80-110) ------------------------------------------------

@@ -47,6 +47,10 @@ struct StepPlan {
   int num_cus = 256;
   DType fwd_mfma = DType::F16;   // MFMA operand dtype the forward / backward GEMMs run
   DType bwd_mfma = DType::F16;
+  // The caller's request, not a decision (resolve_step_plan leaves it false and no other field
+  // depends on it): the backward also writes dL/dtau to StepBuffers::dtau (launch_tau_grad, the
+  // step's last launch). World 1 only.
+  bool tau_grad = false;
 };
 
 // The only caller of the *_eligible functions and *_enabled toggles outside the launchers' own
@@ -78,7 +82,8 @@ struct StepBuffers {
   float2* fold_pre = nullptr;    // folded LSE scratch [Rpad] (raw)
   int* fold_cnt = nullptr;       // (z) [Rpad / 64 + 1] (raw)
   float* dotp = nullptr;         // dot partials [dot_slots][Rpad] (fuse)
-  float* dot = nullptr;          // [Rpad] (fuse)
+  float* dot = nullptr;          // [Rpad] (fuse, or tau_grad on any plan)
+  float* dtau = nullptr;         // [1] dL/dtau (tau_grad)
   int* dot_cnt = nullptr;        // (z) [2] (dfold)
   void* slabs = nullptr;         // dZ [Rpad][dim_n], fp16 (fp32 plans: fp32); unused when the dZ fuses
   const int4* fwd_tiles = nullptr;
@@ -96,7 +101,7 @@ struct StepBuffers {
 struct StepBufferBytes {
   size_t zq = 0, zq8 = 0, zqt = 0, zq8t = 0, inv = 0, ypos = 0, part = 0, sbuf = 0, cbuf = 0, lse2 = 0, cpos = 0,
          q8_mneg = 0, q8_lmin = 0, block_loss = 0, loss = 4, fold_pre = 0, fold_cnt = 0, dotp = 0, dot = 0,
-         dot_cnt = 0, slabs = 0, small_scratch = 0, ws = 0;
+         dot_cnt = 0, slabs = 0, small_scratch = 0, ws = 0, dtau = 0;
 };
 StepBufferBytes step_buffer_bytes(const StepPlan& p);
 
@@ -112,7 +117,8 @@ struct StepComm {
 
 // The launch sequence of one step, asynchronous on `stream`: prep -> forward GEMM (with or
 // without the diagonal remainder and the LSE fold) -> LSE; coefficient pass -> optional dot
-// reduce -> dZ -> optional normalisation backward; or the two small-path launches.
+// reduce -> dZ -> optional normalisation backward; or the two small-path launches. With
+// StepPlan::tau_grad one more launch ends the backward (launch_tau_grad over b.dot).
 // Multi-rank (comm != null): b.zq / zq8 / zqt / lse2 point at the gathered buffers (this rank's
 // slot at g.rank) and ws.sched_cus caps the forward GEMMs that overlap a gather.
 void step_forward(const StepPlan& p, const StepBuffers& b, hipStream_t stream, StepComm* comm = nullptr);

@@ -11,6 +11,7 @@
 //   coef_kernel        -> grad_logits.diagonal() = ...               src/ntxent_kernel.cu:218-221
 //   sim_gemm<DZ>       -> cublasSgemm backward                        src/ntxent_kernel.cu:228-236
 //   norm_bwd_kernel    -> (missing) normalisation backward + grad_out scaling
+//   tau_grad_kernel    -> (missing) d loss / d temperature from the per-row dot of the above
 
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
@@ -705,7 +706,7 @@ __global__ __launch_bounds__(256) void norm_bwd_vec_kernel(const float* __restri
                                                            const Tin* __restrict__ h, const float* __restrict__ inv,
                                                            const float* __restrict__ grad_out, float alpha_base,
                                                            Tin* __restrict__ dh, int d, const _Float16* __restrict__ xs,
-                                                           int nx) {
+                                                           int nx, float* __restrict__ dot_out) {
   __shared__ float red[16];
   const int i = blockIdx.x;
   const float iv = inv[i];
@@ -740,6 +741,7 @@ __global__ __launch_bounds__(256) void norm_bwd_vec_kernel(const float* __restri
     }
   }
   dot = block_sum(dot, red);
+  if (dot_out != nullptr && threadIdx.x == 0) dot_out[i] = dot;  // z_i . g_i for launch_tau_grad
   Tin* di = dh + (long long)i * d;
   const float s = alpha * iv;
 #pragma unroll
@@ -760,7 +762,7 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const float* __restrict__
                                                        const Tin* __restrict__ h, const float* __restrict__ inv,
                                                        const float* __restrict__ grad_out, float alpha_base,
                                                        Tin* __restrict__ dh, int d, const _Float16* __restrict__ xs,
-                                                       int nx) {
+                                                       int nx, float* __restrict__ dot_out) {
   const _Float16* xi = xs + (long long)blockIdx.x * ldo;
   __shared__ float red[16];
   const int i = blockIdx.x;
@@ -776,6 +778,7 @@ __global__ __launch_bounds__(256) void norm_bwd_kernel(const float* __restrict__
     dot += to_f32<Tin>(hi[e]) * iv * g;
   }
   dot = block_sum(dot, red);
+  if (dot_out != nullptr && threadIdx.x == 0) dot_out[i] = dot;
   Tin* di = dh + (long long)i * d;
   for (int e = threadIdx.x; e < d; e += 256) {
     float g = 0.f;
@@ -805,6 +808,28 @@ __global__ __launch_bounds__(256) void dot_reduce_kernel(const float* __restrict
     for (int g = 0; g < 8; ++g) t += part[g][threadIdx.x];
     dot[blockIdx.x * 32 + threadIdx.x] = t;
   }
+}
+
+// Temperature gradient: dtau = grad_out * scale * sum_{i < rows} dot_i, scale = -1 / (2 R tau^2)
+// (dL/dtau = sum_ij dL/dS_ij (-cos_ij / tau^2) and sum_ij (P_ij - [j = p(i)]) cos_ij = sum_i dot_i / 2,
+// cos being symmetric). One block: thread t sums rows t, t + 1024, ... in order, then a fixed
+// halving tree over the 1024 partials (deterministic, no atomics). fp64 accumulation: at most
+// 32768 terms of one sign, and the 33 adds per thread are not what the launch costs.
+constexpr int kTauGradThreads = 1024;
+__global__ __launch_bounds__(kTauGradThreads) void tau_grad_kernel(const float* __restrict__ dot, int rows,
+                                                                   const float* __restrict__ grad_out, double scale,
+                                                                   float* __restrict__ dtau) {
+  __shared__ double part[kTauGradThreads];
+  double t = 0.0;
+  for (int i = threadIdx.x; i < rows; i += kTauGradThreads) t += (double)dot[i];
+  part[threadIdx.x] = t;
+  __syncthreads();
+#pragma unroll
+  for (int n = kTauGradThreads / 2; n > 0; n >>= 1) {
+    if ((int)threadIdx.x < n) part[threadIdx.x] += part[threadIdx.x + n];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dtau[0] = (float)((double)grad_out[0] * scale * part[0]);
 }
 
 }  // namespace dev
@@ -1828,9 +1853,18 @@ void launch_dz_view(DType comp, const void* a, long long a_panel_tiles, const vo
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
+void launch_tau_grad(const float* dot, const float* grad_out, float* dtau, const Geometry& g, hipStream_t stream) {
+  NTXENT_CHECK(dot != nullptr && grad_out != nullptr && dtau != nullptr, "tau_grad: null buffer");
+  const double tau = (double)g.temperature;
+  const double scale = -1.0 / (2.0 * (double)g.global_rows * tau * tau);
+  hipLaunchKernelGGL(dev::tau_grad_kernel, dim3(1), dim3(dev::kTauGradThreads), 0, stream, dot, g.rows, grad_out, scale,
+                     dtau);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
 void launch_norm_bwd(DType in, const float* slabs, int nslabs, const void* h, const float* inv,
                      const float* grad_out, void* dh, const Geometry& g, hipStream_t stream,
-                     const void* xslabs, int nx) {
+                     const void* xslabs, int nx, float* dot_out) {
   const _Float16* xs = static_cast<const _Float16*>(xslabs);
   if (xs == nullptr) nx = 0;
   const float alpha_base = (float)(1.0 / ((double)g.global_rows * g.temperature));
@@ -1843,16 +1877,16 @@ void launch_norm_bwd(DType in, const float* slabs, int nslabs, const void* h, co
     Tin* dp = static_cast<Tin*>(dh);
     if (vec && nch == 1)
       hipLaunchKernelGGL((dev::norm_bwd_vec_kernel<Tin, 1>), dim3(g.rows), dim3(256), 0, stream, slabs, nslabs, ss,
-                         ldo, hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx);
+                         ldo, hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx, dot_out);
     else if (vec && nch == 2)
       hipLaunchKernelGGL((dev::norm_bwd_vec_kernel<Tin, 2>), dim3(g.rows), dim3(256), 0, stream, slabs, nslabs, ss,
-                         ldo, hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx);
+                         ldo, hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx, dot_out);
     else if (vec)
       hipLaunchKernelGGL((dev::norm_bwd_vec_kernel<Tin, 4>), dim3(g.rows), dim3(256), 0, stream, slabs, nslabs, ss,
-                         ldo, hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx);
+                         ldo, hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx, dot_out);
     else
       hipLaunchKernelGGL((dev::norm_bwd_kernel<Tin>), dim3(g.rows), dim3(256), 0, stream, slabs, nslabs, ss, ldo,
-                         hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx);
+                         hp, inv, grad_out, alpha_base, dp, g.dim, xs, nx, dot_out);
   });
   NTXENT_HIP_CHECK(hipGetLastError());
 }

@@ -52,6 +52,7 @@ struct SmallParams {
   float* slabs;       // [nT][nS][64 * dk] fp32 partial dZ (bwd, nS > 1)
   const float* grad_out;
   void* dh;
+  float* dot_out;     // [R] z_i . g_i of the normalisation backward (optional: launch_tau_grad reads it)
   int R, n_half, ldk, d, dk, nT, Rp64, nS;
   float y_scale;      // log2(e) / tau
   float loss_scale;   // 1 / R
@@ -488,6 +489,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_bwd_kernel(const SmallPar
       dot += z[eb] * acc[eb][r];
     }
     dot = row16_sum(dot);
+    if (p.dot_out != nullptr && ok && r16 == 0) p.dot_out[gr] = dot;
     const float sc = alpha * iv;
 #pragma unroll
     for (int eb = 0; eb < NEB; ++eb) {
@@ -617,7 +619,7 @@ void launch_small_fwd(DType in, DType comp, const void* h, void* zq, float* inv,
 
 void launch_small_bwd(DType in, DType comp, const void* zq, const void* h, const float* inv, const float* lse2,
                       const float* arow, const float* grad_out, void* dh, void* scratch, const Geometry& g,
-                      hipStream_t stream, int splits) {
+                      hipStream_t stream, int splits, float* dot_out) {
   NTXENT_CHECK(small_path_eligible(g, comp), "small path: problem not eligible");
   if (splits <= 0) splits = small_bwd_splits(g);
   NTXENT_CHECK(splits <= small_nt(g), "small path: more column splits than column blocks");
@@ -628,6 +630,7 @@ void launch_small_bwd(DType in, DType comp, const void* zq, const void* h, const
   p.arow = const_cast<float*>(arow);
   p.grad_out = grad_out;
   p.dh = dh;
+  p.dot_out = dot_out;
   const dim3 grid(p.nT, splits);
   by_nks(g.dim_k, [&](auto nks) {
     constexpr int NKS = decltype(nks)::value;

@@ -41,6 +41,7 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   rank_ = comm ? comm->rank() : 0;
   world_ = comm ? comm->world() : 1;
   g_ = make_geometry(cfg.rows, cfg.dim, world_, rank_, cfg.temperature);
+  NTXENT_CHECK(!cfg.temperature_grad || world_ == 1, "Engine: temperature_grad needs world == 1");
   f8_ = cfg.compute == DType::FP8;
 #ifdef NTXENT_NO_FP8
   if (f8_) throw std::runtime_error("ntxent::Engine: fp8 compute requested but this build has ENABLE_FP8=OFF");
@@ -108,6 +109,7 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
       {(void**)&dotp_, symm_ ? 0 : nb.dotp},
       {(void**)&dot_, symm_ ? 0 : nb.dot},
       {(void**)&dot_cnt_, symm_ ? 0 : nb.dot_cnt},
+      {(void**)&dtau_, nb.dtau},
       {(void**)&fwd_tiles_, ft.size() * sizeof(int4)},
       {(void**)&dz_tiles_, dt.size() * sizeof(int4)},
       {&ws_.ptr, ws_.bytes},
@@ -175,6 +177,7 @@ StepBuffers Engine::buffers(const float* grad_out, void* dh) const {
   b.dotp = dotp_;
   b.dot = dot_;
   b.dot_cnt = dot_cnt_;
+  b.dtau = dtau_;
   b.slabs = slabs_;
   b.fwd_tiles = fwd_tiles_;
   b.dz_tiles = dz_tiles_;
@@ -235,6 +238,24 @@ void Engine::before_dz(hipStream_t s) {
   if (!zqt_pending_) return;
   NTXENT_HIP_CHECK(hipStreamWaitEvent(s, ev_zqt_, 0));
   zqt_pending_ = false;
+}
+
+void Engine::set_temperature(float temperature) {
+  NTXENT_CHECK(world_ == 1, "Engine::set_temperature: single-process engines only (world == 1)");
+  NTXENT_CHECK(temperature > 0.f, "temperature must be positive");
+  cfg_.temperature = temperature;
+  g_.temperature = temperature;  // (as make_geometry)
+  g_.inv_temp = 1.0f / temperature;
+  if (exec_) { hipGraphExecDestroy(exec_); exec_ = nullptr; }
+  if (graph_) { hipGraphDestroy(graph_); graph_ = nullptr; }
+}
+
+float Engine::temperature_grad(hipStream_t s) {
+  NTXENT_CHECK(dtau_ != nullptr, "Engine::temperature_grad: EngineConfig::temperature_grad is off");
+  float d = 0.f;
+  NTXENT_HIP_CHECK(hipMemcpyAsync(&d, dtau_, 4, hipMemcpyDeviceToHost, s));
+  NTXENT_HIP_CHECK(hipStreamSynchronize(s));
+  return d;
 }
 
 void Engine::capture(const void* h, void* dh, hipStream_t s) {

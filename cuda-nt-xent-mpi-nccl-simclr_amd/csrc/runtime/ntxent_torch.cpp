@@ -93,32 +93,76 @@ static at::Tensor upload_tiles(const std::vector<int4>& v, int device) {
   return cpu.to(torch::Device(torch::kCUDA, device), /*non_blocking=*/false);
 }
 
+// The device tile lists depend on the shape alone: plans that differ only in temperature or
+// compute dtype share one upload (a temperature that moves every step would otherwise upload two
+// lists per step with a blocking copy and keep every one of them).
+namespace {
+struct TileLists {
+  at::Tensor fwd_tiles, dz_tiles;
+  int n_fwd = 0, n_own = 0, n_dz = 0;
+};
+std::atomic<long> g_tile_uploads{0};  // tile_list_uploads(): what the tests count
+
+// caller holds get_plan's lock
+std::shared_ptr<const TileLists> tile_lists(const Geometry& g, int device) {
+  static std::map<std::tuple<int, int, int, int, int>, std::shared_ptr<const TileLists>> cache;
+  auto key = std::make_tuple(g.rows, g.dim, g.world, g.rank, device);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  auto t = std::make_shared<TileLists>();
+  auto ft = build_fwd_tiles(g);
+  t->n_fwd = (int)ft.size();
+  t->n_own = count_own_fwd_tiles(g);
+  t->fwd_tiles = upload_tiles(ft, device);
+  auto dt = build_dz_tiles(g);
+  t->n_dz = (int)dt.size();
+  t->dz_tiles = upload_tiles(dt, device);
+  g_tile_uploads.fetch_add(1);
+  cache.emplace(key, t);
+  return t;
+}
+constexpr size_t kMaxPlans = 64;  // per-temperature Plan objects kept (least recently used goes first)
+}  // namespace
+
 std::shared_ptr<Plan> get_plan(int rows, int dim, int world, int rank, double temperature,
                                const std::string& compute, int device) {
   static std::mutex mu;
-  static std::map<std::tuple<int, int, int, int, float, int, int>, std::shared_ptr<Plan>> cache;
+  struct Entry {
+    std::shared_ptr<Plan> plan;
+    unsigned long long used = 0;
+  };
+  static std::map<std::tuple<int, int, int, int, float, int, int>, Entry> cache;
+  static unsigned long long tick = 0;
   const DType comp = choose_compute(at::kFloat, compute != "fp32" && compute != "float32", compute);
   auto key = std::make_tuple(rows, dim, world, rank, (float)temperature, (int)comp, device);
   std::lock_guard<std::mutex> lock(mu);
   auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
+  if (it != cache.end()) {
+    it->second.used = ++tick;
+    return it->second.plan;
+  }
   auto p = std::make_shared<Plan>();
   p->g = make_geometry(rows, dim, world, rank, (float)temperature);
   p->comp = comp;
   p->device = device;
   const DeviceInfo& di = device_info(device);
   p->num_cus = di.num_cus;
-  auto ft = build_fwd_tiles(p->g);
-  p->n_fwd = (int)ft.size();
-  p->n_own = count_own_fwd_tiles(p->g);
-  p->fwd_tiles = upload_tiles(ft, device);
-  auto dt = build_dz_tiles(p->g);
-  p->n_dz = (int)dt.size();
-  p->dz_tiles = upload_tiles(dt, device);
+  const auto tl = tile_lists(p->g, device);
+  p->n_fwd = tl->n_fwd;
+  p->n_own = tl->n_own;
+  p->fwd_tiles = tl->fwd_tiles;
+  p->n_dz = tl->n_dz;
+  p->dz_tiles = tl->dz_tiles;
   StepOverrides small_on;  // eligibility, whatever set_small_path says
   small_on.small_path = 1;
   p->small = resolve_step_plan(p->g, DType::F16, comp, true, p->num_cus, small_on).small;
-  cache.emplace(key, p);
+  if (cache.size() >= kMaxPlans) {  // (a plan still in use stays alive through its shared_ptr)
+    auto lru = cache.begin();
+    for (auto c = cache.begin(); c != cache.end(); ++c)
+      if (c->second.used < lru->second.used) lru = c;
+    cache.erase(lru);
+  }
+  cache.emplace(key, Entry{p, ++tick});
   return p;
 }
 
@@ -649,10 +693,11 @@ std::vector<at::Tensor> fused_forward(const at::Tensor& h, double T, const std::
   return {loss, zq, zqt, inv, lse2, sc, cpos};
 }
 
-at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::optional<at::Tensor>& zqt_in,
-                          const at::Tensor& inv,
-                          const at::Tensor& lse2, const c10::optional<at::Tensor>& sc_in, const at::Tensor& cpos,
-                          const at::Tensor& grad_out, double T) {
+// want_tau: also dL/dtau (StepPlan::tau_grad), a 0-d fp32 tensor; undefined otherwise.
+static std::pair<at::Tensor, at::Tensor> fused_backward_impl(
+    const at::Tensor& h, const at::Tensor& zq, const c10::optional<at::Tensor>& zqt_in, const at::Tensor& inv,
+    const at::Tensor& lse2, const c10::optional<at::Tensor>& sc_in, const at::Tensor& cpos, const at::Tensor& grad_out,
+    double T, bool want_tau) {
   const at::DeviceGuard guard(h.device());
   const DType rows_dt = to_dtype(zq.scalar_type());
   auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, T, dtype_name(rows_dt), h.device().index());
@@ -666,8 +711,9 @@ at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::
   ov.small_path = !zqt.defined();
   ov.fp8_backward = q8;
   // (sc undefined: a second backward (retain_graph), which recomputes the cosines)
-  const StepPlan sp = resolve_step_plan(g, to_dtype(h.scalar_type()), f8 ? DType::FP8 : rows_dt, sc.defined(),
-                                        P->num_cus, ov);
+  StepPlan sp = resolve_step_plan(g, to_dtype(h.scalar_type()), f8 ? DType::FP8 : rows_dt, sc.defined(),
+                                  P->num_cus, ov);
+  sp.tau_grad = want_tau;
   NTXENT_CHECK(sp.small == !zqt.defined(), "fused_backward: missing ZqT for a large-problem plan");
   NTXENT_CHECK(sp.q8 == q8 && (!q8 || cpos.numel() == 2 * (long)g.rows_pad + 64),
                "fused_backward (fp8): kept cosines and the forward's Q8Stats required");
@@ -678,7 +724,7 @@ at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::
   b.inv = static_cast<float*>(inv.data_ptr());
   b.lse2 = static_cast<float*>(lse2.data_ptr());
   b.cpos = static_cast<float*>(cpos.data_ptr());
-  at::Tensor zr = zq, cb, dotp, dot, slabs;
+  at::Tensor zr = zq, cb, dotp, dot, slabs, dtau;
   if (!sp.small) {
     // (a raw-operand forward returns no unit rows: a second backward rebuilds them to recompute S)
     if (!sp.keep_cos && zq.numel() == 0) zr = prep(h, *P, c10::nullopt, c10::nullopt)[0];
@@ -696,11 +742,33 @@ at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::
     }
     b.sbuf = sc.defined() ? sc.data_ptr() : nullptr;
   }
+  if (sp.tau_grad) {  // the unfused and the small paths store their per-row dot as well
+    if (!dot.defined()) dot = mk(b.dot, h, nb.dot, at::kFloat);
+    dtau = at::empty({}, opts(h, at::kFloat));
+    b.dtau = dtau.data_ptr<float>();
+  }
   b.zq = zr.data_ptr();
   b.grad_out = go.data_ptr<float>();
   b.dh = dh.data_ptr();
   step_backward(sp, b, cur_stream(h));
-  return dh;
+  return {dh, dtau};
+}
+
+at::Tensor fused_backward(const at::Tensor& h, const at::Tensor& zq, const c10::optional<at::Tensor>& zqt_in,
+                          const at::Tensor& inv,
+                          const at::Tensor& lse2, const c10::optional<at::Tensor>& sc_in, const at::Tensor& cpos,
+                          const at::Tensor& grad_out, double T) {
+  return fused_backward_impl(h, zq, zqt_in, inv, lse2, sc_in, cpos, grad_out, T, false).first;
+}
+
+// fused_backward plus the temperature gradient: (dh, dtau), dtau = dL/dtau times grad_out, a 0-d
+// fp32 tensor. dh is bitwise fused_backward's.
+std::tuple<at::Tensor, at::Tensor> fused_backward_tau(const at::Tensor& h, const at::Tensor& zq,
+                                                      const c10::optional<at::Tensor>& zqt_in, const at::Tensor& inv,
+                                                      const at::Tensor& lse2, const c10::optional<at::Tensor>& sc_in,
+                                                      const at::Tensor& cpos, const at::Tensor& grad_out, double T) {
+  auto r = fused_backward_impl(h, zq, zqt_in, inv, lse2, sc_in, cpos, grad_out, T, true);
+  return {r.first, r.second};
 }
 
 // ---- reference-compatible API (src/binding_new.cpp:5-20) -------------------------------
@@ -844,7 +912,7 @@ class NativeEngine {
  public:
   NativeEngine(int rows, int dim, double T, const std::string& input, const std::string& compute,
                const std::string& negatives, int rank, int world, const std::string& uid, int device, bool keep_cos,
-               int comm_reserve_cus, std::shared_ptr<RcclComm> comm = nullptr)
+               int comm_reserve_cus, std::shared_ptr<RcclComm> comm = nullptr, bool temperature_grad = false)
       : device_(device) {
     NTXENT_CHECK(world >= 1 && rank >= 0 && rank < world, "NativeEngine: bad rank/world");
     NTXENT_CHECK(negatives == "symmetric" || negatives == "allgather", "negatives must be symmetric|allgather");
@@ -866,6 +934,7 @@ class NativeEngine {
     cfg.comm_reserve_cus = comm_reserve_cus;
     cfg.negatives = negatives == "symmetric" ? Negatives::kSymmetric : Negatives::kAllGather;
     cfg.device = device;
+    cfg.temperature_grad = temperature_grad;
     in_ = to_scalar(cfg.input);
     eng_ = std::make_unique<Engine>(cfg, comm_.get());
   }
@@ -923,6 +992,25 @@ class NativeEngine {
     // the engine's backward reads the forward input: point it back at the captured one
     h_ = gh_;
     eng_->replay(cur_stream(gh_));
+  }
+  // world 1: the next forward / backward run at `t` (same arena); a captured graph is dropped
+  void set_temperature(double t) {
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(device_);
+    eng_->set_temperature((float)t);
+    gh_ = at::Tensor();
+    gdh_ = at::Tensor();
+  }
+  double temperature() const { return eng_->geometry().temperature; }
+  bool captured() const { return eng_->captured(); }
+  // dL/dtau of the last backward as a 0-d fp32 tensor (stream-ordered copy of the engine's slot)
+  at::Tensor temperature_grad() const {
+    NTXENT_CHECK(h_.defined(), "no backward yet");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(device_);
+    const float* src = eng_->temperature_grad_device();
+    NTXENT_CHECK(src != nullptr, "NativeEngine.temperature_grad: built without temperature_grad=True");
+    at::Tensor out = at::empty({}, h_.options().dtype(at::kFloat));
+    NTXENT_HIP_CHECK(hipMemcpyAsync(out.data_ptr(), src, sizeof(float), hipMemcpyDeviceToDevice, cur_stream(h_)));
+    return out;
   }
   size_t device_bytes() const { return eng_->device_bytes(); }
   bool symmetric() const { return eng_->symmetric(); }
@@ -1011,17 +1099,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("abort", &ntxent::RcclComm::abort);
   py::class_<NativeEngine>(m, "NativeEngine")
       .def(py::init<int, int, double, const std::string&, const std::string&, const std::string&, int, int,
-                    const std::string&, int, bool, int, std::shared_ptr<ntxent::RcclComm>>(),
+                    const std::string&, int, bool, int, std::shared_ptr<ntxent::RcclComm>, bool>(),
            py::arg("rows"), py::arg("dim"), py::arg("temperature"), py::arg("input") = "bf16",
            py::arg("compute") = "auto", py::arg("negatives") = "symmetric", py::arg("rank") = 0, py::arg("world") = 1,
            py::arg("uid") = std::string(), py::arg("device") = 0, py::arg("keep_cos") = true,
-           py::arg("comm_reserve_cus") = 8, py::arg("comm") = py::none())
+           py::arg("comm_reserve_cus") = 8, py::arg("comm") = py::none(), py::arg("temperature_grad") = false)
       .def("forward", &NativeEngine::forward, py::arg("h"))
       .def("backward", &NativeEngine::backward, py::arg("grad_out") = py::none())
       .def("loss_tensor", &NativeEngine::loss_tensor)
       .def("step", &NativeEngine::step, py::arg("h"))
       .def("capture", &NativeEngine::capture, py::arg("h"))
       .def("replay", &NativeEngine::replay)
+      .def("set_temperature", &NativeEngine::set_temperature, py::arg("temperature"))
+      .def("temperature_grad", &NativeEngine::temperature_grad)
+      .def_property_readonly("temperature", &NativeEngine::temperature)
+      .def_property_readonly("captured", &NativeEngine::captured)
       .def_property_readonly("device_bytes", &NativeEngine::device_bytes)
       .def_property_readonly("symmetric", &NativeEngine::symmetric)
       .def_property_readonly("small", &NativeEngine::small)
@@ -1082,6 +1174,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_forward", &fused_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto",
         py::arg("keep_cos") = true);
   m.def("fused_backward", &fused_backward);
+  m.def("fused_backward_tau", &fused_backward_tau);
+  m.def("tile_list_uploads", []() { return g_tile_uploads.load(); });
   m.def("set_small_path", &ntxent::set_small_path, py::arg("on"));
   m.def("small_path_enabled", &ntxent::small_path_enabled);
   m.def("set_small_splits", &ntxent::set_small_splits, py::arg("n"));

@@ -51,6 +51,10 @@ StepBufferBytes step_buffer_bytes(const StepPlan& p) {
   StepBufferBytes n;
   n.zq = W * Rp * g.ld_k * cs;
   n.inv = n.ypos = R * 4;
+  if (p.tau_grad) {  // every plan then has the per-row dot (the unfused paths store it as well)
+    n.dot = Rp * 4;
+    n.dtau = 4;
+  }
   if (p.small) {
     n.lse2 = n.cpos = (size_t)small_rows_pad(g) * 4;
     n.small_scratch = small_scratch_bytes(g, std::max(small_bwd_splits(g), p.small_splits));
@@ -70,7 +74,7 @@ StepBufferBytes step_buffer_bytes(const StepPlan& p) {
   n.fold_pre = g.world == 1 ? Rp * sizeof(float2) : 0;
   n.fold_cnt = g.world == 1 ? (Rp / 64 + 1) * sizeof(int) : 0;
   n.dotp = p.fuse ? Rp * (size_t)dot_slots(g) * 4 : 0;
-  n.dot = p.fuse ? Rp * 4 : 0;
+  n.dot = p.fuse || p.tau_grad ? Rp * 4 : 0;
   n.dot_cnt = p.fuse ? 2 * sizeof(int) : 0;
   n.slabs = Rp * g.dim_n * (p.bwd != DType::F32 ? 2 : 4);
   n.ws = gemm_workspace_bytes(std::max(p.n_fwd, p.n_dz), p.num_cus);
@@ -160,13 +164,25 @@ void step_forward(const StepPlan& p, const StepBuffers& b, hipStream_t s, StepCo
   if (fault_armed("nonfinite")) NTXENT_HIP_CHECK(hipMemsetAsync(b.loss, 0xFF, 4, s));  // NaN
 }
 
+namespace {
+// dL/dtau from the per-row dot the backward has just left in b.dot: the step's last launch
+void tau_grad(const StepBuffers& b, const Geometry& g, hipStream_t s) {
+  NTXENT_TRACE("ntxent.tau_grad");
+  launch_tau_grad(b.dot, b.grad_out, b.dtau, g, s);
+}
+}  // namespace
+
 void step_backward(const StepPlan& p, const StepBuffers& b, hipStream_t s, StepComm* comm) {
   const Geometry& g = p.g;
+  NTXENT_CHECK(!p.tau_grad || (g.world == 1 && comm == nullptr && b.dot && b.dtau),
+               "step_backward: the temperature gradient needs one rank and the dot / dtau buffers");
+  float* dot_out = p.tau_grad ? b.dot : nullptr;  // the unfused paths store their per-row dot
   if (p.small) {
     NTXENT_TRACE("ntxent.small_bwd");
     fault_point("dz");
     launch_small_bwd(p.in, p.comp, b.zq, b.h, b.inv, b.lse2, b.cpos, b.grad_out, b.dh, b.small_scratch, g, s,
-                     p.small_splits);
+                     p.small_splits, dot_out);
+    if (p.tau_grad) tau_grad(b, g, s);
     return;
   }
   const char* zq_local = slot(b.zq, (size_t)g.rows_pad * g.ld_k * dtype_size(p.bwd), g);
@@ -206,16 +222,21 @@ void step_backward(const StepPlan& p, const StepBuffers& b, hipStream_t s, StepC
                          p.fuse ? &nf : nullptr, &q8, b.cpos)
              : launch_dz(p.bwd, b.cbuf, b.zqt, b.dz_tiles, p.n_dz, b.slabs, b.ws, g, s,
                          /*out_f16=*/p.bwd != DType::F32, p.fuse ? &nf : nullptr, nullptr, nullptr, p.half_c);
-    if (fused) return;  // dh written by the dZ epilogue
+    if (fused) {  // dh written by the dZ epilogue; b.dot is complete once that launch has finished
+      if (p.tau_grad) tau_grad(b, g, s);
+      return;
+    }
   }
   {
     NTXENT_TRACE("ntxent.norm_bwd");
     fault_point("norm_bwd");
     if (p.bwd != DType::F32)  // fp16 dZ slab (reduced-precision plans)
-      launch_norm_bwd(p.in, nullptr, 0, b.h, b.inv, b.grad_out, b.dh, g, s, b.slabs, 1);
+      launch_norm_bwd(p.in, nullptr, 0, b.h, b.inv, b.grad_out, b.dh, g, s, b.slabs, 1, dot_out);
     else
-      launch_norm_bwd(p.in, static_cast<const float*>(b.slabs), 1, b.h, b.inv, b.grad_out, b.dh, g, s);
+      launch_norm_bwd(p.in, static_cast<const float*>(b.slabs), 1, b.h, b.inv, b.grad_out, b.dh, g, s, nullptr, 0,
+                      dot_out);
   }
+  if (p.tau_grad) tau_grad(b, g, s);
 }
 
 }  // namespace ntxent

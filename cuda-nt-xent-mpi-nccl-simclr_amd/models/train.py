@@ -1,6 +1,7 @@
 """CLI: SimCLR pre-training on synthetic images, one process per GPU.
 
   python -m ntxent_amd.models.train --steps 50 --batch 256
+  python -m ntxent_amd.models.train --steps 50 --batch 256 --learnable-temperature true   # one GPU
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
       -m ntxent_amd.models.train --steps 200 --batch 512 --ckpt-dir ckpt/ --ckpt-every 50
 """

@@ -45,6 +45,9 @@ class TrainConfig:
     proj_hidden: int = 2048
     proj_out: int = 128
     temperature: float = 0.5
+    # one GPU only: the loss owns log_temperature (NTXentLoss(learnable_temperature=True)), trained
+    # in a parameter group of its own with no weight decay and no LARS adaptation
+    learnable_temperature: bool = False
     lr: float = 0.3                  # base LR, scaled by global batch / 256
     weight_decay: float = 1e-6
     warmup_steps: int = 10
@@ -117,6 +120,9 @@ class SimCLRTrainer:
     def __init__(self, cfg: TrainConfig, device: Optional[torch.device] = None):
         self.cfg = cfg
         self.world, self.rank = _dist()
+        if cfg.learnable_temperature and self.world > 1:
+            raise NotImplementedError("learnable_temperature is supported on one GPU only (world == 1): the "
+                                      "distributed loss does not reduce the temperature gradient across ranks")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
@@ -138,9 +144,11 @@ class SimCLRTrainer:
             self.model = torch.nn.parallel.DistributedDataParallel(
                 model, device_ids=[device.index] if device.type == "cuda" else None, bucket_cap_mb=64)
         self.opt = build_optimizer(cfg, self.model, self.world)
-        self.base_lrs = [g["lr"] for g in self.opt.param_groups]
         self.loss_fn = NTXentLoss(cfg.temperature, compute=cfg.compute, distributed=self.world > 1,
-                                  negatives=cfg.negatives)
+                                  negatives=cfg.negatives, learnable_temperature=cfg.learnable_temperature).to(device)
+        if cfg.learnable_temperature:
+            self.opt.add_param_group({"params": [self.loss_fn.log_temperature], "weight_decay": 0.0, "lars": False})
+        self.base_lrs = [g["lr"] for g in self.opt.param_groups]
         self.data = SyntheticImages(cfg, device, self.rank)
         self.aug = AugmentConfig(out_size=cfg.image_size)
         self.mem = GPUMemoryTracker() if device.type == "cuda" else None
@@ -151,6 +159,9 @@ class SimCLRTrainer:
             if last is not None:
                 st = load_checkpoint(last, model=self.model, optimizer=self.opt, map_location=device)
                 self.step = st["step"]
+                if cfg.learnable_temperature and "log_temperature" in st["extra"]:
+                    with torch.no_grad():
+                        self.loss_fn.log_temperature.fill_(float(st["extra"]["log_temperature"]))
 
     def train_step(self) -> Dict:
         if self.stream is None:
@@ -190,12 +201,20 @@ class SimCLRTrainer:
         dt = time.perf_counter() - t0
         rec = {"step": self.step, "loss": lv, "lr": self.opt.param_groups[0]["lr"], "step_ms": dt * 1e3,
                "images_per_s": cfg.batch * self.world / dt}
+        if cfg.learnable_temperature:  # the temperature the next step uses
+            rec["temperature"] = float(self.loss_fn.current_temperature().detach())
         if not math.isfinite(lv):
             raise FloatingPointError(f"non-finite loss at step {self.step}")
         self.step += 1
         if cfg.ckpt_dir and cfg.ckpt_every and self.step % cfg.ckpt_every == 0:
+            conf = asdict(cfg)
+            extra = {"config": conf}
+            if cfg.learnable_temperature:
+                extra["log_temperature"] = float(self.loss_fn.log_temperature.detach())
+            else:  # option off: the checkpoint is what it was before the option existed
+                del conf["learnable_temperature"]
             save_checkpoint(Path(cfg.ckpt_dir) / f"ckpt_{self.step}.pt", model=self.model, optimizer=self.opt,
-                            step=self.step, extra={"config": asdict(cfg)}, rank=self.rank)
+                            step=self.step, extra=extra, rank=self.rank)
         return rec
 
     def fit(self, steps: Optional[int] = None) -> List[Dict]:

@@ -15,6 +15,7 @@ Execution (single process; see ``parallel.distributed`` for global-batch negativ
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -43,15 +44,45 @@ def resolve_compute(dtype: torch.dtype, use_mixed_precision: bool = False, compu
     return "fp16"
 
 
+def temperature_value(temperature) -> float:
+    """tau as a host float. A one-element tensor is read with ``.item()``: one host sync when it
+    lives on the GPU, none for a CPU tensor."""
+    if isinstance(temperature, torch.Tensor):
+        if temperature.numel() != 1:
+            raise ValueError("temperature must be a float or a one-element tensor")
+        return float(temperature.detach().item())
+    return float(temperature)
+
+
+def temperature_wants_grad(temperature) -> bool:
+    """True for a tensor temperature autograd tracks: a leaf that requires grad, or a result with
+    a ``grad_fn`` such as ``log_scale.exp()``."""
+    return isinstance(temperature, torch.Tensor) and (temperature.requires_grad or temperature.grad_fn is not None)
+
+
+def refuse_temperature_grad(temperature, where: str) -> None:
+    """The data-parallel paths do not all-reduce the per-rank dL/dtau partials yet: refuse a
+    temperature that requires grad instead of detaching it silently."""
+    if temperature_wants_grad(temperature):
+        raise NotImplementedError(
+            f"{where}: a temperature that requires grad is supported on one GPU only (ntxent_loss); the "
+            "distributed paths do not reduce its gradient across ranks. Pass a float or a detached tensor.")
+
+
 class NTXentFunction(torch.autograd.Function):
-    """loss = NTXent(h) for stacked views h = [h1; h2] on one GPU."""
+    """loss = NTXent(h) for stacked views h = [h1; h2] on one GPU.
+
+    ``tau`` is None, or the one-element temperature tensor whose gradient is wanted: the backward
+    then also returns dL/dtau (``fused_backward_tau``) in that tensor's dtype, shape and device."""
 
     @staticmethod
-    def forward(ctx, h: torch.Tensor, temperature: float, compute: str, keep_logits: bool):
+    def forward(ctx, h: torch.Tensor, temperature: float, compute: str, keep_logits: bool,
+                tau: Optional[torch.Tensor] = None):
         C = _ext.load()
         h = h.contiguous()
         loss, zq, zqt, inv, lse2, sc, cpos = C.fused_forward(h, float(temperature), compute, bool(keep_logits))
         ctx.temperature = float(temperature)
+        ctx.tau = None if tau is None else (tau.dtype, tau.device, tau.shape)
         ctx.sc = sc if keep_logits else None  # released by the first backward
         ctx.save_for_backward(h, zq, zqt, inv, lse2, cpos)
         ctx.mark_non_differentiable()
@@ -62,16 +93,24 @@ class NTXentFunction(torch.autograd.Function):
         C = _ext.load()
         h, zq, zqt, inv, lse2, cpos = ctx.saved_tensors
         sc, ctx.sc = ctx.sc, None  # a second backward (retain_graph) recomputes the cosines
-        dh = C.fused_backward(h, zq, zqt, inv, lse2, sc, cpos, grad_out.reshape(1), ctx.temperature)
-        return dh, None, None, None
+        if ctx.tau is None or not ctx.needs_input_grad[4]:
+            dh = C.fused_backward(h, zq, zqt, inv, lse2, sc, cpos, grad_out.reshape(1), ctx.temperature)
+            return dh, None, None, None, None
+        dh, dtau = C.fused_backward_tau(h, zq, zqt, inv, lse2, sc, cpos, grad_out.reshape(1), ctx.temperature)
+        dtype, device, shape = ctx.tau
+        return dh, None, None, None, dtau.to(device=device, dtype=dtype).reshape(shape)
 
 
-def ntxent_loss(h: torch.Tensor, temperature: float = 0.07, *, use_mixed_precision: bool = False,
+def ntxent_loss(h: torch.Tensor, temperature=0.07, *, use_mixed_precision: bool = False,
                 compute: str = "auto", keep_logits: bool = True, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """NT-Xent loss of stacked views ``h = [h1; h2]`` (or ``h1=h, z2=h2``).
 
     Args:
-      temperature: tau.
+      temperature: tau, a float or a one-element tensor. A tensor that requires grad (or has a
+        ``grad_fn``, e.g. ``log_scale.exp()``) receives dL/dtau from the backward, in its own dtype
+        and on its own device; loss, dh and the plan are bitwise those of the same float. The
+        kernels take tau by value, so reading a GPU tensor's value costs one host sync per forward;
+        a CPU tensor costs none.
       use_mixed_precision: fp32 inputs are computed in fp16 (fp32 accumulate) if True.
       compute: override the compute dtype: ``auto|fp32|fp16|bf16|fp8``. ``fp8`` runs the forward
         similarity GEMM on block-scaled e4m3 MFMA (per-row amax power-of-two scales) and the backward in fp16; the
@@ -87,9 +126,16 @@ def ntxent_loss(h: torch.Tensor, temperature: float = 0.07, *, use_mixed_precisi
     if _use_reference(h):
         if h.is_cuda and os.environ.get("NTXENT_ALLOW_REFERENCE", "0") != "1":
             raise RuntimeError("NTXENT_FORCE_REFERENCE requires NTXENT_ALLOW_REFERENCE=1")
+        if isinstance(temperature, torch.Tensor):  # autograd carries the temperature's gradient
+            if temperature.numel() != 1:
+                raise ValueError("temperature must be a float or a one-element tensor")
+            temperature = temperature.reshape(()).to(h.device)
         return reference.ntxent_loss(h, temperature)
     comp = resolve_compute(h.dtype, use_mixed_precision, compute)
-    return NTXentFunction.apply(h, float(temperature), comp, bool(keep_logits) or comp == "fp8")
+    keep = bool(keep_logits) or comp == "fp8"
+    if temperature_wants_grad(temperature):
+        return NTXentFunction.apply(h, temperature_value(temperature), comp, keep, temperature)
+    return NTXentFunction.apply(h, temperature_value(temperature), comp, keep, None)
 
 
 class NTXentLoss(torch.nn.Module):
@@ -97,10 +143,15 @@ class NTXentLoss(torch.nn.Module):
 
     With ``distributed=True`` negatives come from the whole data-parallel group over RCCL/xGMI
     (``negatives``: "allgather", "symmetric" or "ring"), see :mod:`parallel`.
+
+    ``learnable_temperature=True`` (one GPU only): the module owns an fp32 parameter
+    ``log_temperature``, initialised to ``log(temperature)``, and evaluates the loss at
+    ``log_temperature.exp().clamp(*temperature_bounds)``; its gradient comes from the same backward.
     """
 
     def __init__(self, temperature: float = 0.07, use_mixed_precision: bool = False, compute: str = "auto",
-                 keep_logits: bool = True, distributed: bool = False, group=None, negatives: str = "allgather"):
+                 keep_logits: bool = True, distributed: bool = False, group=None, negatives: str = "allgather",
+                 learnable_temperature: bool = False, temperature_bounds=(0.01, 1.0)):
         super().__init__()
         self.negatives = negatives
         self.temperature = float(temperature)
@@ -109,6 +160,22 @@ class NTXentLoss(torch.nn.Module):
         self.keep_logits = keep_logits
         self.distributed = distributed
         self.group = group
+        self.learnable_temperature = bool(learnable_temperature)
+        self.temperature_bounds = (float(temperature_bounds[0]), float(temperature_bounds[1]))
+        if self.learnable_temperature:
+            if distributed:
+                raise NotImplementedError(
+                    "NTXentLoss: learnable_temperature is supported on one GPU only; the distributed paths do "
+                    "not reduce the temperature gradient across ranks")
+            if not 0.0 < self.temperature_bounds[0] <= self.temperature_bounds[1]:
+                raise ValueError("temperature_bounds must be 0 < low <= high")
+            self.log_temperature = torch.nn.Parameter(torch.tensor(math.log(self.temperature), dtype=torch.float32))
+
+    def current_temperature(self):
+        """The temperature the next call uses: a float, or the clamped ``log_temperature.exp()``."""
+        if not self.learnable_temperature:
+            return self.temperature
+        return self.log_temperature.exp().clamp(*self.temperature_bounds)
 
     def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
         h = z1 if z2 is None else torch.cat([z1, z2], 0)
@@ -118,11 +185,14 @@ class NTXentLoss(torch.nn.Module):
             return dist_ntxent_loss(h, self.temperature, group=self.group, compute=self.compute,
                                     use_mixed_precision=self.use_mixed_precision, keep_logits=self.keep_logits,
                                     negatives=self.negatives)
-        return ntxent_loss(h, self.temperature, use_mixed_precision=self.use_mixed_precision,
+        return ntxent_loss(h, self.current_temperature(), use_mixed_precision=self.use_mixed_precision,
                            compute=self.compute, keep_logits=self.keep_logits)
 
     def extra_repr(self) -> str:
-        return f"temperature={self.temperature}, compute={self.compute}, distributed={self.distributed}"
+        s = f"temperature={self.temperature}, compute={self.compute}, distributed={self.distributed}"
+        if self.learnable_temperature:
+            s += f", learnable_temperature=True, temperature_bounds={self.temperature_bounds}"
+        return s
 
 
 # ---- reference-compatible raw op API (src/binding_new.cpp:5-20) --------------------------

@@ -79,6 +79,26 @@ def ntxent_backward_analytic(h: torch.Tensor, temperature: float, grad_out: floa
     return inv.unsqueeze(1) * (dz - z * dot)
 
 
+def ntxent_temperature_grad_analytic(h: torch.Tensor, temperature: float,
+                                     grad_out: float | torch.Tensor = 1.0) -> torch.Tensor:
+    """Closed-form d loss / d tau (what the HIP ``tau_grad`` launch implements), a 0-d tensor.
+
+    With R = 2N rows, cos = z z^T and C = P + P^T - 2 I_pos:
+    dL/dtau = -(1 / (2 R tau^2)) sum_i dot_i, dot_i = sum_j C_ij cos_ij = z_i . (C z)_i,
+    the per-row scalar of the normalisation backward.
+    """
+    R = h.shape[0]
+    tau = float(temperature)
+    z, _ = normalize(h)
+    S = logits(h, tau)
+    P = torch.exp(S - torch.logsumexp(S, dim=1, keepdim=True))
+    pos = positive_index(R, h.device)
+    C = P + P.t()
+    C[torch.arange(R, device=h.device), pos] -= 2.0
+    dot = (z * (C @ z)).sum(1)
+    return -torch.as_tensor(grad_out, dtype=h.dtype, device=h.device) * dot.sum() / (2.0 * R * tau * tau)
+
+
 # ---------------------------------------------------------------------------------------
 # Data-parallel layout: rank r holds h_r = [h1_r; h2_r] (2n rows); positives are rank-local.
 # ---------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _ext, reference
-from ..ops.ntxent import resolve_compute
+from ..ops.ntxent import refuse_temperature_grad, resolve_compute
 from .commstats import comm_reserve_cus, span
 
 
@@ -205,6 +205,7 @@ def dist_ntxent_loss(h_local: torch.Tensor, temperature: float = 0.07, *, group=
     backward, overlap on -- else the torch-driven stages), ``"engine"`` (required; raises if not
     eligible) or ``"torch"`` (the Python-driven stages over ``torch.distributed``).
     """
+    refuse_temperature_grad(temperature, "dist_ntxent_loss")
     if negatives not in ("allgather", "ring", "symmetric"):
         raise ValueError("negatives must be 'allgather', 'symmetric' or 'ring'")
     if impl not in ("auto", "engine", "torch"):
@@ -299,4 +300,5 @@ class _CpuDistFn(torch.autograd.Function):
 
 def cpu_dist_ntxent_loss(h_local: torch.Tensor, temperature: float = 0.07, group=None,
                          backward_mode: str = "symmetric") -> torch.Tensor:
+    refuse_temperature_grad(temperature, "cpu_dist_ntxent_loss")
     return _CpuDistFn.apply(h_local, float(temperature), group, backward_mode)

@@ -37,6 +37,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _ext
+from ..ops.ntxent import refuse_temperature_grad
 
 _DT = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
 _lock = threading.Lock()
@@ -158,6 +159,7 @@ def engine_ntxent_loss(h_local: torch.Tensor, temperature: float, *, group=None,
                        negatives: str = "symmetric", keep_logits: bool = True, comm_reserve_cus: int = 8) -> torch.Tensor:
     """Global NT-Xent over ``group`` on the native engine (see the module docstring);
     ``compute`` is a resolved compute dtype (``ops.ntxent.resolve_compute``)."""
+    refuse_temperature_grad(temperature, "engine_ntxent_loss")
     h = h_local.contiguous()
     slot = engine_for(h.shape[0], h.shape[1], temperature, h.dtype, compute, negatives, keep_logits, group,
                       h.device.index, comm_reserve_cus)

@@ -8,6 +8,8 @@ exposes it to torch users:
 
 * ``NativeNTXent(rows, dim)``: one GPU. ``step(h)`` returns ``(loss, dh)`` for the
   ``[view1; view2]`` rows ``h``. ``capture(h)`` / ``replay()`` replays a step from a hipGraph.
+  ``temperature_grad=True`` adds d loss / d temperature (``temperature_grad()``), and
+  ``set_temperature(t)`` moves the temperature between steps without a new engine.
 * ``NativeNTXent.from_process_group(rows, dim)``: one rank per process. The RCCL unique id is
   made on rank 0 and broadcast through the torch.distributed store. The
   engine then runs its own RCCL communicator, outside torch's ProcessGroup.
@@ -34,15 +36,18 @@ class NativeNTXent:
     def __init__(self, rows: int, dim: int, temperature: float = 0.07, *, dtype: torch.dtype = torch.bfloat16,
                  compute: str = "auto", negatives: str = "symmetric", device: Optional[int] = None,
                  keep_cos: bool = True, comm_reserve_cus: int = 8, rank: int = 0, world: int = 1,
-                 uid: bytes = b""):
+                 uid: bytes = b"", temperature_grad: bool = False):
         if dtype not in _DT:
             raise TypeError(f"dtype must be one of {list(_DT)}")
+        if temperature_grad and int(world) != 1:
+            raise NotImplementedError("NativeNTXent: temperature_grad is supported on one GPU only (world == 1)")
         C = _ext.load()
         dev = torch.cuda.current_device() if device is None else int(device)
         self.rows, self.dim, self.temperature, self.dtype = int(rows), int(dim), float(temperature), dtype
         self.device = torch.device("cuda", dev)
         self._e = C.NativeEngine(self.rows, self.dim, self.temperature, _DT[dtype], compute, negatives, int(rank),
-                                 int(world), uid, dev, bool(keep_cos), int(comm_reserve_cus))
+                                 int(world), uid, dev, bool(keep_cos), int(comm_reserve_cus),
+                                 temperature_grad=bool(temperature_grad))
 
     @classmethod
     def from_process_group(cls, rows: int, dim: int, temperature: float = 0.07, *, group=None, **kw) -> "NativeNTXent":
@@ -88,6 +93,21 @@ class NativeNTXent:
     def replay(self) -> torch.Tensor:
         self._e.replay()
         return self._e.loss_tensor()
+
+    def set_temperature(self, temperature: float) -> None:
+        """Run the following steps at ``temperature`` (one GPU only; no reallocation). A captured
+        graph holds the old value in its kernel arguments and is dropped: ``captured`` turns False."""
+        self._e.set_temperature(float(temperature))
+        self.temperature = float(temperature)
+
+    def temperature_grad(self) -> torch.Tensor:
+        """d loss / d temperature of the preceding backward, step or replay (times ``grad_out``) as
+        a 0-d fp32 tensor; needs ``temperature_grad=True`` at construction."""
+        return self._e.temperature_grad()
+
+    @property
+    def captured(self) -> bool:
+        return self._e.captured
 
     @property
     def device_bytes(self) -> int:

@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _ext
-from ..ops.ntxent import resolve_compute
+from ..ops.ntxent import refuse_temperature_grad, resolve_compute
 from .commstats import comm_reserve_cus, span
 from .distributed import _all_gather_into, _is_gloo, _world
 
@@ -143,6 +143,7 @@ def ring_ntxent_loss(h_local: torch.Tensor, temperature: float = 0.07, *, group=
                      use_mixed_precision: bool = False) -> torch.Tensor:
     """Global NT-Xent over the group with ring-passed negatives (O(local) memory); same value
     and gradient as :func:`parallel.distributed.dist_ntxent_loss`."""
+    refuse_temperature_grad(temperature, "ring_ntxent_loss")
     if not h_local.is_cuda:
         from .distributed import cpu_dist_ntxent_loss
 

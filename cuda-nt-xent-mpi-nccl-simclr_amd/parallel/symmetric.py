@@ -39,7 +39,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _ext, reference
-from ..ops.ntxent import resolve_compute
+from ..ops.ntxent import refuse_temperature_grad, resolve_compute
 from .commstats import comm_reserve_cus, span
 from .distributed import _all_gather_into, _is_gloo, _world
 
@@ -371,6 +371,7 @@ def sym_ntxent_loss(h_local: torch.Tensor, temperature: float = 0.07, *, group=N
                     use_mixed_precision: bool = False) -> torch.Tensor:
     """Global NT-Xent over the group with each rank pair's similarity block computed once;
     same value and gradient as :func:`parallel.distributed.dist_ntxent_loss`."""
+    refuse_temperature_grad(temperature, "sym_ntxent_loss")
     W, _ = _world(group)
     if not h_local.is_cuda:
         return cpu_sym_ntxent_loss(h_local, temperature, group=group)
@@ -484,4 +485,5 @@ class _CpuSymFn(torch.autograd.Function):
 
 
 def cpu_sym_ntxent_loss(h_local: torch.Tensor, temperature: float = 0.07, group=None, tile: int = 256) -> torch.Tensor:
+    refuse_temperature_grad(temperature, "cpu_sym_ntxent_loss")
     return _CpuSymFn.apply(h_local, float(temperature), group, int(tile))
