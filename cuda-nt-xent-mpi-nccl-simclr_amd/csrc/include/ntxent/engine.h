@@ -7,7 +7,7 @@
 //   * one arena allocation per (shape, dtype, world) sized up front — no allocation or host
 //     sync inside a step, so a whole fwd+bwd step is hipGraph-capturable (capture()/replay())
 //     and replays with no per-kernel launch overhead; the step itself is the shared launch
-//     sequence of step.h (the symmetric mode has its own, engine_sym.cpp);
+//     sequence of step.h (the symmetric mode's is sym_step.h, driven by engine_sym.cpp);
 //   * data parallel through a Comm (RCCL over xGMI): prep writes this rank's normalised rows
 //     straight into its slot of the gathered buffer, the all-gathers run on a high-priority
 //     comm stream while the own-rank (upper-triangular) tiles are computed, and only the
@@ -22,12 +22,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
-#include <utility>
 #include <vector>
 
 #include "ntxent/comm.h"
 #include "ntxent/ntxent.h"
 #include "ntxent/step.h"
+#include "ntxent/sym_step.h"
 
 namespace ntxent {
 
@@ -141,31 +141,26 @@ class Engine : private StepComm {
   float* dotp_ = nullptr;      // dot partials [Rpad][dot_slots] (StepPlan::fuse)
   float* dot_ = nullptr;       // dot [Rpad]
   float* dtau_ = nullptr;      // dL/dtau [1] (EngineConfig::temperature_grad)
-  // symmetric data-parallel mode (Negatives::kSymmetric, engine_sym.cpp)
+  // symmetric data-parallel mode (Negatives::kSymmetric): the schedule and the launches are
+  // sym_step.h's, engine_sym.cpp runs the exchanges between them
   bool symm_ = false;
-  std::vector<SymJob> jobs_, inc_;
-  int nch_ = 1, nfull_ = 0;
-  std::vector<std::pair<int, int>> segs_;  // (first, count) of each row chunk's cross tiles
+  SymPlan sym_;
   float2* part_x_ = nullptr;               // column partials of the cross tiles
   float2* fold_pre_ = nullptr;             // folded LSE scratch (RawRows::fold_pre / fold_cnt)
   int* fold_cnt_ = nullptr;
   float2* xsend_ = nullptr;                // packed column partials of the k-split block (one run per row tile
   float2* xrecv_ = nullptr;                // otherwise: one send/recv per partner instead of one per row tile)
   char* mbuf_ = nullptr;                   // partners' mirrored coefficient blocks
-  char* contrib_ = nullptr;                // partners' gradient contributions (nfull + split blocks)
-  char* recv_ = nullptr;                   // received contributions [inc][Rpad][dim_n]
-  size_t ccs_ = 2;                         // bytes per contribution element (fp16, fp32 plans: 4)
-  int4* dz_rows_ = nullptr;                // dz_view tile lists: see init_sym
-  std::vector<std::pair<int, int>> dz_ranges_;
+  char* contrib_ = nullptr;                // partners' gradient contributions, one slab per job
+  char* recv_ = nullptr;                   // received fp16 contributions [incoming][Rpad][dim_n]
+  int4* dz_rows_ = nullptr;                // device copy of SymPlan::dz_rows
   std::vector<hipEvent_t> ev_chunk_;
   hipEvent_t ev_f16_ = nullptr, ev_x_ = nullptr, ev_xdone_ = nullptr, ev_c_ = nullptr, ev_cdone_ = nullptr;
   void init_sym();
-  void forward_sym(const void* h, hipStream_t s);
+  SymBuffers sym_buffers(const float* grad_out, void* dh) const;
+  GemmWorkspace ws_overlap() const;  // ws_ with comm_reserve_cus CUs left free
+  void forward_sym(hipStream_t s);  // of h_
   void backward_sym(const float* grad_out, void* dh, hipStream_t s);
-  const int4* dz_rows(int m0, int m1) const;
-  void dz_view(const char* abuf, long a_tile0, long a_panel_tiles, const char* bbuf, int b_block0, long b_col0,
-               int k_tiles, int m0, int m1, void* out, bool accum, bool out_f16, hipStream_t s,
-               const GemmWorkspace& ws);
   float* q8_mneg_ = nullptr;   // Q8Stats: negatives-only row max [Rpad], min LSE [1]
   float* q8_lmin_ = nullptr;
   char* zq8t_ = nullptr;       // e4m3(256 Zq^T) [dim_n][q8_ldt]

@@ -32,6 +32,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace ntxent {
@@ -106,20 +107,22 @@ enum TileKind : int { kTilePlain = 0, kTileDiag = 1, kTileSymOff = 2, kTileCross
 
 // Symmetric data-parallel mode: rank `rank` computes rows [m0, m1) (its row tiles) x columns
 // [k0, k1) (rank q's row tiles) of the similarity block (rank, q); each unordered rank pair's
-// block is computed once across the group (see parallel/symmetric.py for the assignment).
+// block is computed once across the group (sym_step.h / sym_step.cpp: the one home of the
+// symmetric step, the assignment sym_jobs included).
 struct SymJob {
   int q, m0, m1, k0, k1;
 };
 // Own-block upper triangle (as build_fwd_tiles) followed by the kTileCross tiles of `jobs`
-// grouped by chunk of the partners' row tiles (chunk c = tiles [rt*c/n, rt*(c+1)/n)), each
-// segment in Z-order.
+// grouped by chunk of the partners' row tiles (sym_chunk_bounds), each segment in Z-order.
 std::vector<int4> build_sym_fwd_tiles(const Geometry& g, const std::vector<SymJob>& jobs, int nchunks = 1);
-// The assignment itself (parallel/symmetric.py sym_jobs / sym_incoming / sym_num_chunks): the
-// blocks rank `rank` computes, and the other ranks' jobs that involve its rows (q = the
-// computing rank there). Rows travel in sym_num_chunks(row_tiles) chunks of row tiles.
+// The assignment itself (defined in sym_step.cpp; Python reads it through the sym_plan binding):
+// the blocks rank `rank` computes, and the other ranks' jobs that involve its rows (q = the
+// computing rank there). Rows travel in sym_num_chunks(row_tiles) chunks of row tiles, chunk c
+// being the row tiles [first, second) of sym_chunk_bounds(row_tiles, c, nchunks).
 std::vector<SymJob> sym_jobs(int world, int rank, int row_tiles);
 std::vector<SymJob> sym_incoming(int world, int rank, int row_tiles);
 int sym_num_chunks(int row_tiles);
+std::pair<int, int> sym_chunk_bounds(int row_tiles, int c, int nchunks);
 // Symmetric mode's compact coefficient buffer: a rank writes only the column blocks at distance
 // 0 .. W/2 from itself (its own block, the full partner blocks, the split block), so cbuf holds
 // [row_tiles][sym_c_ld(g)] tiles with global column tile nt at column slot (nt - rank * row_tiles)

@@ -1099,11 +1099,11 @@ std::vector<int4> build_sym_fwd_tiles(const Geometry& g, const std::vector<SymJo
   // one contiguous Z-ordered segment per chunk of the partners' row tiles (sym_chunk_bounds):
   // a chunk's tiles can run as soon as that chunk of every partner's rows has arrived
   for (int c = 0; c < nchunks; ++c) {
-    const int c0 = (int)((long long)g.row_tiles * c / nchunks), c1 = (int)((long long)g.row_tiles * (c + 1) / nchunks);
+    const auto cb = sym_chunk_bounds(g.row_tiles, c, nchunks);
     const size_t first = tiles.size();
     for (const SymJob& j : jobs)
       for (int ti = j.m0; ti < j.m1; ++ti)
-        for (int tj = std::max(j.k0, c0); tj < std::min(j.k1, c1); ++tj)
+        for (int tj = std::max(j.k0, cb.first); tj < std::min(j.k1, cb.second); ++tj)
           tiles.push_back(make_int4(ti, j.q * g.row_tiles + tj, kTileCross, 0));
     zorder(tiles, first, tiles.size());
   }
@@ -1111,31 +1111,6 @@ std::vector<int4> build_sym_fwd_tiles(const Geometry& g, const std::vector<SymJo
 }
 
 int count_own_fwd_tiles(const Geometry& g) { return g.row_tiles * (g.row_tiles + 1) / 2; }
-
-std::vector<SymJob> sym_jobs(int world, int rank, int row_tiles) {
-  std::vector<SymJob> jobs;
-  const int W = world, r = rank, rt = row_tiles;
-  for (int d = 1; d <= (W - 1) / 2; ++d) jobs.push_back(SymJob{(r + d) % W, 0, rt, 0, rt});
-  if (W % 2 == 0 && W > 1) {
-    const int q = (r + W / 2) % W, h = (rt + 1) / 2;
-    const SymJob j = r < q ? SymJob{q, 0, h, 0, rt} : SymJob{q, 0, rt, h, rt};
-    if (j.m0 < j.m1 && j.k0 < j.k1) jobs.push_back(j);
-  }
-  return jobs;
-}
-
-std::vector<SymJob> sym_incoming(int world, int rank, int row_tiles) {
-  std::vector<SymJob> out;
-  for (int p = 0; p < world; ++p) {
-    if (p == rank) continue;
-    for (const SymJob& j : sym_jobs(world, p, row_tiles))
-      if (j.q == rank) out.push_back(SymJob{p, j.m0, j.m1, j.k0, j.k1});
-  }
-  return out;
-}
-
-int sym_num_chunks(int row_tiles) { return std::max(1, std::min(4, row_tiles)); }
-int sym_c_ld(const Geometry& g) { return std::min(g.world, g.world / 2 + 1) * g.row_tiles; }
 
 GemmSchedule make_schedule(int ntiles, int nk, int num_cus) {
   // Whole tiles in data-parallel rounds of G = num_cus blocks; only the remainder tiles

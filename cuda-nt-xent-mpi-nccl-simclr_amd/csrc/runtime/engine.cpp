@@ -17,15 +17,6 @@
 
 namespace ntxent {
 
-// float2 elements of the packed column-partial runs of the jobs whose partner row range is not a
-// whole block (k0 > 0 or k1 < row_tiles: the runs of consecutive row tiles are Rpad apart, not
-// adjacent), see Engine::forward_sym
-static size_t sym_xpack_floats2(const std::vector<SymJob>& jobs, int row_tiles) {
-  size_t n = 0;
-  for (const SymJob& j : jobs)
-    if (j.k1 - j.k0 != row_tiles) n += (size_t)(j.m1 - j.m0) * (j.k1 - j.k0) * kTile;
-  return n;
-}
 namespace {
 
 constexpr size_t kAlign = 256;
@@ -52,10 +43,7 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   symm_ = world_ > 1 && cfg.negatives == Negatives::kSymmetric;
   if (symm_) {
     cfg_.keep_cos = true;  // the coefficient pass reads both blocks' cosines from the forward
-    jobs_ = sym_jobs(world_, rank_, g_.row_tiles);
-    inc_ = sym_incoming(world_, rank_, g_.row_tiles);
-    nch_ = sym_num_chunks(g_.row_tiles);
-    ccs_ = bwd_ == DType::F32 ? 4 : 2;
+    sym_ = make_sym_plan(g_, bwd_, f8_);
   }
   ws_.num_cus = device_info(device_).num_cus;
   ov_.small_path = cfg.small_path;
@@ -66,18 +54,19 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   ov_.fp8_backward = p.q8;
   const StepBufferBytes nb = step_buffer_bytes(p);
 
-  const auto ft = symm_ ? build_sym_fwd_tiles(g_, jobs_, nch_) : build_fwd_tiles(g_);
+  const auto ft = symm_ ? build_sym_fwd_tiles(g_, sym_.jobs, sym_.nchunks) : build_fwd_tiles(g_);
   const auto dt = build_dz_tiles(g_);
   n_fwd_ = (int)ft.size();
   n_own_ = count_own_fwd_tiles(g_);
   n_dz_ = (int)dt.size();
-  NTXENT_CHECK((symm_ || n_fwd_ == p.n_fwd) && n_own_ == p.n_own && n_dz_ == p.n_dz, "Engine: plan / tile list mismatch");
+  NTXENT_CHECK(n_fwd_ == (symm_ ? sym_.n_fwd : p.n_fwd) && n_own_ == p.n_own && n_dz_ == p.n_dz, "Engine: plan / tile list mismatch");
   ws_.bytes = gemm_workspace_bytes(std::max(n_fwd_, n_dz_), ws_.num_cus);
 
-  const size_t Rp = g_.rows_pad;
   struct Slot { void** p; size_t bytes; };
-  // the symmetric mode (engine_sym.cpp) keeps its own cosine / coefficient / slab layouts and
-  // sums received contributions in launch_norm_bwd (no fused normalisation backward)
+  // the symmetric mode (sym_step.h) keeps its own cosine / coefficient / slab layouts and sums
+  // received contributions in launch_norm_bwd (no fused normalisation backward): its rows come
+  // from the plan's SymBufferBytes (all 0 in the other modes)
+  const SymBufferBytes& sb = sym_.bytes;
   const std::vector<Slot> slots = {
       {(void**)&zq_all_, nb.zq},
       {(void**)&zq8_all_, nb.zq8},
@@ -88,24 +77,23 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
       {(void**)&inv_, nb.inv},
       {(void**)&ypos_, nb.ypos},
       {(void**)&part_, nb.part},
-      {(void**)&sbuf_, symm_ ? (size_t)n_fwd_ * kTileElems * cs_ : nb.sbuf},
-      {(void**)&cbuf_, symm_ ? (size_t)g_.row_tiles * sym_c_ld(g_) * kTileElems * cs_ : nb.cbuf},
+      {(void**)&sbuf_, symm_ ? sb.sbuf : nb.sbuf},
+      {(void**)&cbuf_, symm_ ? sb.cbuf : nb.cbuf},
       {(void**)&lse2_all_, nb.lse2},
       {(void**)&cpos_, nb.cpos},
       {(void**)&block_loss_, nb.block_loss},
       {(void**)&loss_, nb.loss},
       {(void**)&one_, 4},
-      // symmetric mode, fp32 plans: the received contributions follow the own slab (one stack)
-      {(void**)&slabs_, symm_ ? Rp * g_.dim_n * 4 * (ccs_ == 4 ? 1 + inc_.size() : 1) : nb.slabs},
+      {(void**)&slabs_, symm_ ? sb.own : nb.slabs},
       {(void**)&fold_pre_, nb.fold_pre},
       {(void**)&fold_cnt_, nb.fold_cnt},
-      {(void**)&part_x_, symm_ ? (size_t)g_.col_tiles * Rp * sizeof(float2) : 0},
-      {(void**)&xsend_, symm_ ? sym_xpack_floats2(jobs_, g_.row_tiles) * sizeof(float2) : 0},
-      {(void**)&xrecv_, symm_ ? sym_xpack_floats2(inc_, g_.row_tiles) * sizeof(float2) : 0},
-      {(void**)&mbuf_, symm_ ? (size_t)std::max(1, world_ / 2) * g_.row_tiles * g_.row_tiles * kTileElems * cs_ : 0},
-      {(void**)&contrib_, symm_ ? (jobs_.size() + 1) * Rp * g_.dim_n * ccs_ : 0},
-      {(void**)&recv_, symm_ && ccs_ == 2 ? inc_.size() * Rp * g_.dim_n * ccs_ : 0},
-      {(void**)&dz_rows_, symm_ ? (size_t)4 * (world_ + 1) * g_.row_tiles * (g_.dim_n / kTile) * sizeof(int4) : 0},
+      {(void**)&part_x_, sb.part_x},
+      {(void**)&xsend_, sb.xsend},
+      {(void**)&xrecv_, sb.xrecv},
+      {(void**)&mbuf_, sb.mbuf},
+      {(void**)&contrib_, sb.contrib},
+      {(void**)&recv_, sb.recv},
+      {(void**)&dz_rows_, sb.dz_rows},
       {(void**)&dotp_, symm_ ? 0 : nb.dotp},
       {(void**)&dot_, symm_ ? 0 : nb.dot},
       {(void**)&dot_cnt_, symm_ ? 0 : nb.dot_cnt},
@@ -128,6 +116,7 @@ Engine::Engine(const EngineConfig& cfg, Comm* comm) : cfg_(cfg), comm_(comm) {
   NTXENT_HIP_CHECK(hipMemset(arena_, 0, total));
   NTXENT_HIP_CHECK(hipMemcpy(fwd_tiles_, ft.data(), ft.size() * sizeof(int4), hipMemcpyHostToDevice));
   NTXENT_HIP_CHECK(hipMemcpy(dz_tiles_, dt.data(), dt.size() * sizeof(int4), hipMemcpyHostToDevice));
+  if (sb.dz_rows) NTXENT_HIP_CHECK(hipMemcpy(dz_rows_, sym_.dz_rows.data(), sb.dz_rows, hipMemcpyHostToDevice));
   const float one = 1.0f;
   NTXENT_HIP_CHECK(hipMemcpy(one_, &one, 4, hipMemcpyHostToDevice));
   if (world_ > 1) {
@@ -188,16 +177,22 @@ StepBuffers Engine::buffers(const float* grad_out, void* dh) const {
   return b;
 }
 
+GemmWorkspace Engine::ws_overlap() const {
+  GemmWorkspace ws = ws_;
+  ws.sched_cus = std::max(1, ws_.num_cus - std::min(cfg_.comm_reserve_cus, ws_.num_cus / 2));
+  return ws;
+}
+
 void Engine::forward(const void* h, hipStream_t s) {
   NTXENT_TRACE("ntxent.forward");
   h_ = h;
   if (symm_) {
-    forward_sym(h, s);
+    forward_sym(s);
     return;
   }
   StepBuffers b = buffers(nullptr, nullptr);
   // both forward launches overlap a gather (rows, then ZqT): leave CUs for the RCCL kernels
-  if (world_ > 1) b.ws.sched_cus = std::max(1, ws_.num_cus - std::min(cfg_.comm_reserve_cus, ws_.num_cus / 2));
+  if (world_ > 1) b.ws = ws_overlap();
   step_forward(plan(), b, s, world_ > 1 ? this : nullptr);
 }
 

@@ -7,7 +7,8 @@
 //     under `ntxent`;
 //   * stage-level ops (prep / fwd_stats / lse / coef / dz / norm_bwd) over a cached `Plan`
 //     (geometry + XCD-ordered tile lists resident on the device), which the Python autograd
-//     Function and the RCCL data-parallel path compose.
+//     Function and the RCCL data-parallel path compose;
+//   * the symmetric data-parallel step's plan and phases (sym_step.h) over a bundle of tensors.
 //
 // No host synchronisation anywhere in these ops: they only enqueue on the current HIP stream.
 #include <torch/extension.h>
@@ -27,6 +28,7 @@
 #include "ntxent/engine.h"
 #include "ntxent/ntxent.h"
 #include "ntxent/step.h"
+#include "ntxent/sym_step.h"
 
 namespace ntxent {
 namespace th {
@@ -465,74 +467,136 @@ at::Tensor dz_block(const at::Tensor& cbuf_block, const at::Tensor& zqt_chunk, c
   return slabs;
 }
 
-// ---- symmetric data-parallel stage ops (parallel/symmetric.py) -----------------------------
-// Every unordered rank pair's similarity block is computed once across the group: the
-// computing rank keeps row AND column partials (kTileCross tiles), forms both coefficient
-// blocks C_{r,q} and C_{q,r} = C_{r,q}^T from its kept cosines, and produces the partner's
-// gradient contribution C_{q,r} Z_r, which the caller sends to q.
-static std::vector<SymJob> to_jobs(const std::vector<std::tuple<int, int, int, int, int>>& jobs) {
-  std::vector<SymJob> v;
-  for (const auto& j : jobs) v.push_back(SymJob{std::get<0>(j), std::get<1>(j), std::get<2>(j), std::get<3>(j), std::get<4>(j)});
-  return v;
+// ---- symmetric data-parallel step (sym_step.h; parallel/symmetric.py, parallel/emulate.py) ----
+// The schedule and the launches are sym_step.cpp's. SymStep is what Python caches per shape: the
+// SymPlan and its two device tile lists, uploaded once. Every phase takes the plan (for the
+// temperature) and a bundle {name: tensor} of the SymBuffers it needs; sym_bufs checks each
+// tensor's dtype and byte size against the plan before its pointer goes anywhere.
+struct SymStep {
+  SymPlan sp;
+  Geometry g;
+  int device = 0;
+  at::Tensor fwd_tiles, dz_rows;
+};
+
+static std::shared_ptr<SymStep> sym_step(const Plan& P) {
+  auto S = std::make_shared<SymStep>();
+  S->sp = make_sym_plan(P.g, P.bwd(), P.comp == DType::FP8);
+  S->g = P.g;
+  S->device = P.device;
+  S->fwd_tiles = upload_tiles(build_sym_fwd_tiles(P.g, S->sp.jobs, S->sp.nchunks), P.device);
+  S->dz_rows = upload_tiles(S->sp.dz_rows, P.device);
+  return S;
 }
 
-at::Tensor sym_fwd_tiles(const Plan& P, const std::vector<std::tuple<int, int, int, int, int>>& jobs, int nchunks) {
-  return upload_tiles(build_sym_fwd_tiles(P.g, to_jobs(jobs), nchunks), P.device);
+struct SymBundle {
+  SymBuffers b;
+  at::Tensor like;       // any tensor of the bundle (device, stream)
+  size_t own_bytes = 0;
+  DType in = DType::BF16;
+};
+
+static SymBundle sym_bufs(const SymStep& S, const Plan& P, const pybind11::dict& d) {
+  const Geometry& g = P.g;
+  const SymPlan& sp = S.sp;
+  NTXENT_CHECK(g.rows == S.g.rows && g.dim == S.g.dim && g.world == S.g.world && g.rank == S.g.rank && P.device == S.device &&
+                   P.bwd() == sp.bwd && (P.comp == DType::FP8) == sp.f8, "symmetric step: plan does not match");
+  SymBundle r;
+  size_t seen = 0;
+  auto take = [&](const char* key, at::ScalarType t, size_t bytes, size_t* at_least = nullptr) -> void* {
+    if (!d.contains(key)) return nullptr;
+    at::Tensor x = d[key].cast<at::Tensor>();
+    check_input(x, key);
+    NTXENT_CHECK(x.scalar_type() == t && (at_least ? x.nbytes() >= bytes : x.nbytes() == bytes),
+                 std::string(key) + ": wrong dtype or size for this symmetric plan");
+    if (at_least) *at_least = x.nbytes();
+    ++seen;
+    r.like = x;
+    return x.data_ptr();
+  };
+  const auto st = to_scalar(sp.bwd), ct = sp.contrib_f16 ? at::kHalf : at::kFloat;
+  const size_t W = g.world, Rp = g.rows_pad, cs = dtype_size(sp.bwd), f2 = sizeof(float2);
+  SymBuffers& b = r.b;
+  if (d.contains("h")) {
+    r.in = to_dtype(d["h"].cast<at::Tensor>().scalar_type());
+    b.h = take("h", to_scalar(r.in), (size_t)g.rows * g.dim * dtype_size(r.in));
+    b.dh = take("dh", to_scalar(r.in), (size_t)g.rows * g.dim * dtype_size(r.in));
+  }
+  b.zq_all = take("zq_all", st, W * Rp * g.ld_k * cs);
+  b.zq8_all = take("zq8_all", at::kByte, W * Rp * g.ld_k8);
+  b.zqt_all = take("zqt_all", st, W * g.dim_n * g.ld_t * cs);
+  b.inv = static_cast<float*>(take("inv", at::kFloat, (size_t)g.rows * 4));
+  b.ypos = static_cast<float*>(take("ypos", at::kFloat, (size_t)g.rows * 4));
+  b.part = static_cast<float2*>(take("part", at::kFloat, g.col_tiles * Rp * f2));
+  b.part_x = static_cast<float2*>(take("part_x", at::kFloat, sp.bytes.part_x));
+  b.sbuf = take("sbuf", st, sp.bytes.sbuf);
+  b.cbuf = take("cbuf", st, sp.bytes.cbuf);
+  b.mbuf = take("mbuf", st, sp.bytes.mbuf);
+  b.lse2_all = static_cast<float*>(take("lse2_all", at::kFloat, W * Rp * 4));
+  b.cpos = static_cast<float*>(take("cpos", at::kFloat, Rp * 4));
+  b.loss = static_cast<float*>(take("loss", at::kFloat, 4));
+  b.contrib = take("contrib", ct, sp.bytes.contrib);
+  // the own dZ needs the own slab; the normalisation backward checks the whole stack (sym_norm_bwd)
+  b.own = static_cast<float*>(take("own", at::kFloat, Rp * g.dim_n * 4, &r.own_bytes));
+  b.recv = take("recv", at::kHalf, sp.bytes.recv);
+  b.grad_out = static_cast<const float*>(take("grad_out", at::kFloat, 4));
+  NTXENT_CHECK(seen == d.size() && seen > 0, "symmetric step: unknown or no buffer in the bundle");
+  b.fwd_tiles = reinterpret_cast<const int4*>(S.fwd_tiles.data_ptr<int>());
+  b.dz_rows = reinterpret_cast<const int4*>(S.dz_rows.data_ptr<int>());
+  return r;
 }
 
-// Forward tiles `tiles` (own block + kTileCross) over the gathered rows: row partials -> part,
-// column partials of cross tiles -> part_x ([col_tiles, rows_pad, 2], see launch_fwd_stats).
-void fwd_stats_sym(const at::Tensor& zq_local, const at::Tensor& zq_all, const at::Tensor& tiles, const Plan& P,
-                   at::Tensor& part, at::Tensor& part_x, const c10::optional<at::Tensor>& sc, int first, int count,
-                   int reserve_cus) {
-  check_input(zq_local, "zq_local");
-  check_input(zq_all, "zq_all");
-  check_input(part, "part");
-  check_input(part_x, "part_x");
-  int n = 0;
-  const int4* tp = tile_ptr(tiles, n);
-  NTXENT_CHECK(first >= 0 && count >= 0 && first + count <= n, "tile range out of bounds");
-  const long pn = (long)P.g.col_tiles * P.g.rows_pad * 2;
-  NTXENT_CHECK(part.numel() == pn && part.scalar_type() == at::kFloat, "part must be float32 [col_tiles, rows_pad, 2]");
-  NTXENT_CHECK(part_x.numel() == pn && part_x.scalar_type() == at::kFloat, "part_x must be float32 [col_tiles, rows_pad, 2]");
-  NTXENT_CHECK(zq_all.numel() == (long)P.g.world * P.g.rows_pad * P.op_ld(),
-               "zq_all must be [world*rows_pad, ld] in the forward operand dtype");
-  const bool keep = sc.has_value() && sc->defined();
-  if (keep) NTXENT_CHECK(sc->numel() == (long)n * kTileElems && sc->scalar_type() == to_scalar(P.bwd()),
-                         "sc must hold one tile per entry of `tiles` in the backward dtype");
-  if (count == 0) return;
-  const at::DeviceGuard guard(zq_local.device());
-  auto ws = gemm_ws(zq_local, count, P, reserve_cus);
-  char* scp = keep ? static_cast<char*>(sc->data_ptr()) + (size_t)first * kTileElems * dtype_size(P.bwd()) : nullptr;
-  launch_fwd_stats(P.comp, zq_local.data_ptr(), zq_all.data_ptr(), tp + first, count,
-                   reinterpret_cast<float2*>(part.data_ptr<float>()), scp, ws, P.g, cur_stream(zq_local), BlockView{},
-                   reinterpret_cast<float2*>(part_x.data_ptr<float>()),
-                   first + count == P.n_own ? std::min(count, own_diag_tail(P.g)) : 0);
+// a phase as a method of SymStep: (plan, bundle, extra arguments...) on the bundle's device and stream
+template <class... A, class F>
+static auto sym_phase(F run) {
+  return [run](const SymStep& S, const Plan& P, const pybind11::dict& d, A... a) {
+    SymBundle x = sym_bufs(S, P, d);
+    const at::DeviceGuard guard(x.like.device());
+    run(S, P, x, cur_stream(x.like), a...);
+  };
 }
 
-// Kept cosines of `tiles` -> own coefficient tiles in cbuf ([row_tiles][col_tiles] tiles) and the
-// partners' mirrored blocks in mbuf ([max(1, world/2)][row_tiles][row_tiles] tiles, one slot per partner).
-void coef_sym(const at::Tensor& sbuf, const at::Tensor& tiles, const at::Tensor& lse2_all, const at::Tensor& cpos,
-              const Plan& P, at::Tensor& cbuf, at::Tensor& mbuf) {
-  check_input(sbuf, "sbuf");
-  check_input(cbuf, "cbuf");
-  check_input(mbuf, "mbuf");
-  int n = 0;
-  const int4* tp = tile_ptr(tiles, n);
-  const auto st = to_scalar(P.bwd());
-  NTXENT_CHECK(sbuf.numel() == (long)n * kTileElems && sbuf.scalar_type() == st, "sbuf must hold one tile per entry");
-  NTXENT_CHECK(cbuf.numel() == (long)P.g.row_tiles * sym_c_ld(P.g) * kTileElems && cbuf.scalar_type() == st,
-               "cbuf must be [row_tiles * sym_c_ld] tiles (compact symmetric layout)");
-  // partner slots (q - rank - 1) mod W of the cross tiles run 0 .. W/2 - 1 (parallel/symmetric.py)
-  NTXENT_CHECK(mbuf.numel() == (long)std::max(1, P.g.world / 2) * P.g.row_tiles * P.g.row_tiles * kTileElems &&
-                   mbuf.scalar_type() == st, "mbuf must be [max(1, world/2) * row_tiles * row_tiles] tiles");
-  NTXENT_CHECK(lse2_all.numel() == (long)P.g.world * P.g.rows_pad, "lse2_all must be [world*rows_pad]");
-  if (n == 0) return;
-  const at::DeviceGuard guard(sbuf.device());
-  launch_coef(P.bwd(), sbuf.data_ptr(), cbuf.data_ptr(), lse2_all.data_ptr<float>(), cpos.data_ptr<float>(), tp, n, P.g,
-              cur_stream(sbuf), mbuf.data_ptr());
+// the schedule as Python reads it: lists of tuples in the field order of sym_step.h
+static pybind11::dict sym_plan_dict(const SymPlan& p) {
+  namespace py = pybind11;
+  auto jobs = [](const std::vector<SymJob>& v) {
+    py::list l;
+    for (const SymJob& j : v) l.append(py::make_tuple(j.q, j.m0, j.m1, j.k0, j.k1));
+    return l;
+  };
+  auto xfers = [](const std::vector<SymXfer>& v) {
+    py::list l;
+    for (const SymXfer& x : v) l.append(py::make_tuple(x.send, x.peer, x.slot0, x.slot1, x.t0, x.t1, x.pack_off));
+    return l;
+  };
+  auto calls = [](const std::vector<SymDzCall>& v) {
+    py::list l;
+    for (const SymDzCall& c : v)
+      l.append(py::make_tuple(c.mirror, c.a_tile0, c.a_panel_tiles, c.b_block0, c.b_col0, c.b_kblk_cols, c.k_tiles, c.m0, c.m1,
+                              c.out, c.accum, c.rows_off));
+    return l;
+  };
+  py::dict r, nb;
+  r["world"] = p.world; r["rank"] = p.rank; r["row_tiles"] = p.row_tiles; r["contrib_f16"] = p.contrib_f16;
+  r["jobs"] = jobs(p.jobs); r["incoming"] = jobs(p.incoming);
+  r["nchunks"] = p.nchunks; r["nfull"] = p.nfull; r["split"] = p.split;
+  r["n_own"] = p.n_own; r["n_fwd"] = p.n_fwd; r["c_ld"] = p.c_ld;
+  py::list segs, rows, dzr;
+  for (const auto& sg : p.segs) segs.append(py::make_tuple(sg.first, sg.second));
+  for (const auto& c : p.rows) rows.append(xfers(c));
+  for (const int4& t : p.dz_rows) dzr.append(py::make_tuple(t.x, t.y));
+  r["segs"] = segs; r["rows"] = rows; r["rows_f16"] = xfers(p.rows_f16);
+  r["col_partials"] = xfers(p.col_partials); r["contribs"] = xfers(p.contribs);
+  r["partner_dz"] = calls(p.partner_dz); r["own_dz"] = calls(p.own_dz); r["dz_rows"] = dzr;
+  nb["sbuf"] = p.bytes.sbuf; nb["cbuf"] = p.bytes.cbuf; nb["mbuf"] = p.bytes.mbuf; nb["part_x"] = p.bytes.part_x;
+  nb["slab"] = p.bytes.slab; nb["contrib"] = p.bytes.contrib; nb["recv"] = p.bytes.recv; nb["own"] = p.bytes.own;
+  nb["xsend"] = p.bytes.xsend; nb["xrecv"] = p.bytes.xrecv; nb["dz_rows"] = p.bytes.dz_rows;
+  r["bytes"] = nb;
+  return r;
 }
 
+// A general dZ view as a stage op (the symmetric step resolves its own calls in sym_step.cpp; this
+// one serves a plain GEMM with reserved CUs, tests/test_gpu_production.py):
 // out[row tiles m0..m1) (+)= A * B with A = tiles of `abuf` starting at tile index a_tile0 (row
 // panels a_panel_tiles tiles apart; row tile mt at a_tile0 + mt * a_panel_tiles), K = k_tiles * 256
 // columns of B = `bbuf` (ZqT blocks [nblk, dim_n, ld_t], or one [dim_n, ld_t]) starting at block
@@ -586,31 +650,6 @@ void dz_view(const at::Tensor& abuf, long a_tile0, long a_panel_tiles, const at:
   auto ws = gemm_ws(abuf, (int)sub.size(0), P, reserve_cus);
   launch_dz_view(P.bwd(), a, a_panel_tiles, b, kblk_cols, blk, k_tiles, reinterpret_cast<const int4*>(sub.data_ptr<int>()),
                  (int)sub.size(0), out.data_ptr(), accum, ws, P.g, cur_stream(abuf), out_f16);
-}
-
-// norm_bwd over a stack of partial dZ slabs [nslabs, rows_pad, dim_n] fp32, plus optional
-// fp16 slabs `xslabs` [nx, rows_pad, dim_n] (received partner contributions), summed in order.
-at::Tensor norm_bwd_slabs(const at::Tensor& slabs, const at::Tensor& h, const at::Tensor& inv, const at::Tensor& grad_out,
-                          const Plan& P, const c10::optional<at::Tensor>& xslabs) {
-  check_input(h, "h");
-  check_input(slabs, "slabs");
-  NTXENT_CHECK(slabs.dim() == 3 && slabs.size(1) == P.g.rows_pad && slabs.size(2) == P.g.dim_n &&
-                   slabs.scalar_type() == at::kFloat, "slabs must be float32 [n, rows_pad, dim_n]");
-  const void* xp = nullptr;
-  int nx = 0;
-  if (xslabs.has_value() && xslabs->defined() && xslabs->numel() > 0) {
-    check_input(*xslabs, "xslabs");
-    NTXENT_CHECK(xslabs->dim() == 3 && xslabs->size(1) == P.g.rows_pad && xslabs->size(2) == P.g.dim_n &&
-                     xslabs->scalar_type() == at::kHalf, "xslabs must be float16 [n, rows_pad, dim_n]");
-    xp = xslabs->data_ptr();
-    nx = (int)xslabs->size(0);
-  }
-  const at::DeviceGuard guard(h.device());
-  auto go = grad_out.to(at::kFloat).contiguous();
-  auto dh = at::empty_like(h);
-  launch_norm_bwd(to_dtype(h.scalar_type()), slabs.data_ptr<float>(), (int)slabs.size(0), h.data_ptr(),
-                  inv.data_ptr<float>(), go.data_ptr<float>(), dh.data_ptr(), P.g, cur_stream(h), xp, nx);
-  return dh;
 }
 
 // ---- single-process fused flows ------------------------------------------------------
@@ -1080,7 +1119,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_property_readonly("compute_dtype", &Plan::compute_dtype)
       .def_property_readonly("backward_dtype", &Plan::backward_dtype_name)
       .def_property_readonly("ld_k8", [](const Plan& p) { return p.g.ld_k8; })
-      .def_property_readonly("sym_c_ld", [](const Plan& p) { return sym_c_ld(p.g); })
       .def_readonly("n_fwd_tiles", &Plan::n_fwd)
       .def_readonly("n_own_tiles", &Plan::n_own)
       .def_readonly("n_dz_tiles", &Plan::n_dz)
@@ -1161,16 +1199,44 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tiles"), py::arg("lse2_all"), py::arg("cpos"), py::arg("plan"), py::arg("c_ld"), py::arg("c_tile0"),
         py::arg("reserve_cus") = 0);
   m.def("dz_block", &dz_block, py::arg("cbuf_block"), py::arg("zqt_chunk"), py::arg("plan"), py::arg("reserve_cus") = 0);
-  m.def("sym_fwd_tiles", &sym_fwd_tiles, py::arg("plan"), py::arg("jobs"), py::arg("nchunks") = 1);
-  m.def("fwd_stats_sym", &fwd_stats_sym, py::arg("zq_local"), py::arg("zq_all"), py::arg("tiles"), py::arg("plan"),
-        py::arg("part"), py::arg("part_x"), py::arg("sc"), py::arg("first"), py::arg("count"), py::arg("reserve_cus") = 0);
-  m.def("coef_sym", &coef_sym, py::arg("sbuf"), py::arg("tiles"), py::arg("lse2_all"), py::arg("cpos"), py::arg("plan"),
-        py::arg("cbuf"), py::arg("mbuf"));
   m.def("dz_view", &dz_view, py::arg("abuf"), py::arg("a_tile0"), py::arg("a_panel_tiles"), py::arg("bbuf"),
         py::arg("b_block0"), py::arg("b_col0"), py::arg("k_tiles"), py::arg("m0"), py::arg("m1"), py::arg("out"),
         py::arg("accum"), py::arg("plan"), py::arg("reserve_cus") = 0);
-  m.def("norm_bwd_slabs", &norm_bwd_slabs, py::arg("slabs"), py::arg("h"), py::arg("inv"), py::arg("grad_out"),
-        py::arg("plan"), py::arg("xslabs") = py::none());
+  // the symmetric step (sym_step.h): one cached object per shape, its phases over a tensor bundle
+  {
+    const auto plan = py::arg("plan"), bufs = py::arg("bufs");
+    const auto reserve = py::arg("reserve_cus") = 0;
+    py::class_<SymStep, std::shared_ptr<SymStep>>(m, "SymStep")
+        .def_property_readonly("plan", [](const SymStep& S) { return sym_plan_dict(S.sp); })
+        .def("prep", sym_phase<>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s) {
+          ntxent::sym_prep(S.sp, P.g, x.in, x.b, s);
+        }), plan, bufs)
+        .def("fwd_tiles_range", sym_phase<int, int, int>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s,
+                                                            int first, int count, int reserve_cus) {
+          ntxent::sym_fwd_tiles(S.sp, P.g, P.comp, x.b, first, count, gemm_ws(x.like, count, P, reserve_cus), s);
+        }), plan, bufs, py::arg("first"), py::arg("count"), reserve)
+        .def("lse", sym_phase<>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s) {
+          x.b.block_loss = static_cast<float*>(device_scratch(x.like, (size_t)ntxent::lse_scratch_floats(P.g) * 4, 1).data_ptr());
+          ntxent::sym_lse(S.sp, P.g, x.b, s);
+        }), plan, bufs)
+        .def("transpose_partners", sym_phase<>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s) {
+          ntxent::sym_transpose_partners(S.sp, P.g, x.b, s);
+        }), plan, bufs)
+        .def("coef", sym_phase<>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s) {
+          ntxent::sym_coef(S.sp, P.g, x.b, s);
+        }), plan, bufs)
+        .def("partner_grads", sym_phase<int>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s, int reserve_cus) {
+          ntxent::sym_partner_grads(S.sp, P.g, x.b, gemm_ws(x.like, P.n_dz, P, reserve_cus), s);
+        }), plan, bufs, reserve)
+        .def("own_grads", sym_phase<int>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s, int reserve_cus) {
+          ntxent::sym_own_grads(S.sp, P.g, x.b, gemm_ws(x.like, P.n_dz, P, reserve_cus), s);
+        }), plan, bufs, reserve)
+        .def("norm_bwd", sym_phase<>([](const SymStep& S, const Plan& P, SymBundle& x, hipStream_t s) {
+          NTXENT_CHECK(x.own_bytes == S.sp.bytes.own, "own: must be the fp32 slab (fp32 plans: the stack with the received slabs)");
+          ntxent::sym_norm_bwd(S.sp, P.g, x.in, x.b, s);
+        }), plan, bufs);
+  }
+  m.def("sym_step", &sym_step, py::arg("plan"));
   m.def("fused_forward", &fused_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto",
         py::arg("keep_cos") = true);
   m.def("fused_backward", &fused_backward);
@@ -1221,11 +1287,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dz_tile_list", [tiles_to_list](int rows, int dim, int world, int rank) {
     return tiles_to_list(ntxent::build_dz_tiles(ntxent::make_geometry(rows, dim, world, rank, 0.07f)));
   }, py::arg("rows"), py::arg("dim"), py::arg("world") = 1, py::arg("rank") = 0);
-  m.def("sym_fwd_tile_list", [tiles_to_list](int rows, int dim, int world, int rank,
-                                             const std::vector<std::tuple<int, int, int, int, int>>& jobs, int nchunks) {
-    return tiles_to_list(
-        ntxent::build_sym_fwd_tiles(ntxent::make_geometry(rows, dim, world, rank, 0.07f), to_jobs(jobs), nchunks));
-  }, py::arg("rows"), py::arg("dim"), py::arg("world"), py::arg("rank"), py::arg("jobs"), py::arg("nchunks") = 1);
+  m.def("sym_fwd_tile_list", [tiles_to_list](int rows, int dim, int world, int rank) {
+    const auto g = ntxent::make_geometry(rows, dim, world, rank, 0.07f);
+    const auto p = ntxent::make_sym_plan(g, ntxent::DType::F16, false);
+    return tiles_to_list(ntxent::build_sym_fwd_tiles(g, p.jobs, p.nchunks));
+  }, py::arg("rows"), py::arg("dim"), py::arg("world"), py::arg("rank"));
+  // the schedule of the symmetric step (sym_step.h) of one rank
+  m.def("sym_plan", [](int rows, int dim, int world, int rank, const std::string& compute) {
+    const ntxent::DType comp = parse_dtype_name(compute);
+    return sym_plan_dict(ntxent::make_sym_plan(ntxent::make_geometry(rows, dim, world, rank, 0.07f),
+                                               ntxent::backward_dtype(comp), comp == ntxent::DType::FP8));
+  }, py::arg("rows"), py::arg("dim"), py::arg("world"), py::arg("rank"), py::arg("compute") = "fp16");
   m.def("schedule", [](int ntiles, int nk, int num_cus) {
     const auto s = ntxent::make_schedule(ntiles, nk, num_cus);
     py::dict r;

@@ -113,11 +113,12 @@ def emulated_ring_forward_backward(shards: Sequence[torch.Tensor], temperature: 
 
 def emulated_sym_forward_backward(shards: Sequence[torch.Tensor], temperature: float, *, compute: str = "auto",
                                   grad_out: float = 1.0) -> Tuple[torch.Tensor, List[torch.Tensor]]:
-    """The symmetric data-parallel stage ops (:mod:`parallel.symmetric`) for W virtual ranks on
-    one device: each rank computes only its assigned cross blocks; the point-to-point
-    exchanges (column partials, partner gradient contributions) become copies."""
-    from .symmetric import (sym_coef, sym_grad_slabs, sym_jobs, sym_norm_bwd, sym_own_grad, sym_partner_grads,
-                            sym_tiles)
+    """The symmetric data-parallel step (csrc/runtime/sym_step.cpp, as :mod:`parallel.symmetric`
+    drives it) for W virtual ranks on one device: each rank computes only its assigned cross
+    blocks; the point-to-point exchanges of the plan (column partials, partner gradient
+    contributions) become copies, and the rows need none (every rank writes its own slot)."""
+    from .symmetric import (TILE, sym_contrib_views, sym_forward_bufs, sym_grad_slabs, sym_lse, sym_norm_bwd,
+                            sym_partner_contribs, sym_step)
 
     C = _ext.load()
     W = len(shards)
@@ -125,51 +126,40 @@ def emulated_sym_forward_backward(shards: Sequence[torch.Tensor], temperature: f
     dev = shards[0].device
     comp = resolve_compute(shards[0].dtype, False, compute)
     plans = [C.get_plan(R, d, W, r, float(temperature), comp, dev.index) for r in range(W)]
+    steps = [sym_step(C, P, dev) for P in plans]
     P0 = plans[0]
-    Rpad, rt = P0.rows_pad, P0.row_tiles
+    Rpad = P0.rows_pad
     f8 = P0.compute_dtype == "fp8"
     cdt = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}[P0.backward_dtype]
     zq_all = torch.empty((W * Rpad, P0.ld_k), dtype=cdt, device=dev)
     zqt_all = torch.empty((W, P0.dim_n, P0.ld_t), dtype=cdt, device=dev)
     zq8_all = torch.empty((W * Rpad, P0.ld_k8), dtype=torch.uint8, device=dev) if f8 else None
-    invs, yposs = [], []
-    for r in range(W):
-        zq = zq_all[r * Rpad:(r + 1) * Rpad]
-        _, inv, ypos, _ = C.prep(shards[r].contiguous(), plans[r], zq, zq8_all[r * Rpad:(r + 1) * Rpad] if f8 else None)
-        C.transpose(zq, plans[r], zqt_all[r])
-        invs.append(inv)
-        yposs.append(ypos)
-    fwd_all = zq8_all if f8 else zq_all
-    parts, parts_x, scs, tiles = [], [], [], []
-    for r in range(W):
-        P = plans[r]
-        t, n = sym_tiles(C, P, dev)
-        part = torch.empty((P.col_tiles, Rpad, 2), dtype=torch.float32, device=dev)
-        part_x = torch.empty_like(part)
-        sc = torch.empty((n * 256 * 256,), dtype=cdt, device=dev)
-        C.fwd_stats_sym(fwd_all[r * Rpad:(r + 1) * Rpad], fwd_all, t, P, part, part_x, sc, 0, n)
-        parts.append(part)
-        parts_x.append(part_x)
-        scs.append(sc)
-        tiles.append(t)
-    for r in range(W):  # "send" column partials to their owners
-        for (q, m0, m1, k0, k1) in sym_jobs(W, r, rt):
-            parts[q][r * rt + m0:r * rt + m1, k0 * 256:k1 * 256].copy_(parts_x[r][q * rt + m0:q * rt + m1, k0 * 256:k1 * 256])
+    hs = [x.contiguous() for x in shards]
+    Bs = [sym_forward_bufs(sp, P, h, zq_all, zqt_all, zq8_all) for (_, sp), P, h in zip(steps, plans, hs)]
+    for (S, _), P, B in zip(steps, plans, Bs):
+        S.prep(P, B)
+    for (S, sp), P, B in zip(steps, plans, Bs):  # every tile in one launch: all rows are there
+        S.fwd_tiles_range(P, B, 0, sp["n_fwd"])
+    for r, (_, sp) in enumerate(steps):  # "send" column partials to their owners
+        for (send, q, s0, s1, t0, t1, _) in sp["col_partials"]:
+            if send:
+                (_, _, d0, d1, _, _, _), = [x for x in steps[q][1]["col_partials"] if not x[0] and x[1] == r]
+                Bs[q]["part"][d0:d1, t0 * TILE:t1 * TILE].copy_(Bs[r]["part_x"][s0:s1, t0 * TILE:t1 * TILE])
     lse2_all = torch.empty((W * Rpad,), dtype=torch.float32, device=dev)
     loss = torch.zeros((), dtype=torch.float32, device=dev)
-    cposs = []
-    for r in range(W):
-        cpos = torch.empty((Rpad,), dtype=torch.float32, device=dev)
-        loss = loss + C.lse(parts[r], yposs[r], lse2_all, cpos, plans[r])
-        cposs.append(cpos)
+    for (S, _), P, B in zip(steps, plans, Bs):
+        loss = loss + sym_lse(S, P, B, lse2_all)  # "all-gather" of LSE + "all-reduce"
     go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
-    bufs = [sym_coef(C, plans[r], W, tiles[r], scs[r], lse2_all, cposs[r]) for r in range(W)]
-    sent = [sym_partner_grads(C, plans[r], W, r, bufs[r][1], zqt_all) for r in range(W)]
+    sent = []
+    for (S, sp), P, B in zip(steps, plans, Bs):
+        sends, _ = sym_contrib_views(sp, sym_partner_contribs(S, sp, P, B), None)
+        sent.append({q: rows for rows, q in sends})
     grads = []
-    for r in range(W):
-        own, recv, views = sym_grad_slabs(plans[r], W, r, dev)
-        sym_own_grad(C, plans[r], W, r, bufs[r][0], zqt_all, own[0])
-        for p, view in views.items():  # "receive"
+    for r, ((S, sp), P, B) in enumerate(zip(steps, plans, Bs)):
+        B["own"], recv = sym_grad_slabs(sp, P, dev)
+        S.own_grads(P, B)
+        for view, p in sym_contrib_views(sp, None, recv)[1]:  # "receive"
             view.copy_(sent[p][r])
-        grads.append(sym_norm_bwd(C, plans[r], own, recv, shards[r].contiguous(), invs[r], go))
+        grads.append(sym_norm_bwd(S, P, B["own"], recv, hs[r], B["inv"], go))
     return loss, grads
+

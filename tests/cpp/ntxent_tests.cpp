@@ -526,6 +526,9 @@ NT_TEST(ThreadCommPrimitives) {  // world 1 semantics of the in-process communic
 NT_TEST(MultiRankSymmetric) {
   // W = 8: the driver's scaling-run world size (3 full partner blocks + a split pair per rank)
   for (int W : {2, 3, 4, 8}) multi_rank_case(W, 512, 128, DType::F16, Negatives::kSymmetric, 2e-3, 2e-2);
+  // one row tile (the upper rank of the split pair has no split job) and three (an odd split)
+  multi_rank_case(4, 256, 64, DType::F16, Negatives::kSymmetric, 2e-3, 2e-2);
+  multi_rank_case(4, 768, 64, DType::F16, Negatives::kSymmetric, 2e-3, 2e-2);
 }
 
 NT_TEST(MultiRankAllGather) {

@@ -5,8 +5,8 @@ Runs exactly the stage ops one rank of a W-GPU job enqueues (rank r's plan, glob
 indices, gathered buffers filled locally instead of by RCCL) and times them with HIP events:
 
   allgather  prep + fwd over the whole row block + lse + coef + dZ (K = W*R) + norm_bwd
-  symmetric  prep + fwd over the own triangle and the assigned cross tiles + lse + coef_sym
-             + partner dZ contributions + own dZ contributions + received adds + norm_bwd
+  symmetric  the phases of the symmetric step (csrc/runtime/sym_step.cpp): prep + own and cross
+             forward tiles + lse + coefficient pass + partner dZ + own dZ + norm_bwd
 
 Communication is excluded (it runs on the RCCL stream beside these kernels); the numbers are
 the compute floor of one rank's step at that W. Usage:
@@ -33,8 +33,8 @@ def main():
     a = ap.parse_args()
 
     from ntxent_amd.ops import _ext
-    from ntxent_amd.parallel.symmetric import (sym_coef, sym_grad_slabs, sym_norm_bwd, sym_own_grad, sym_partner_grads,
-                                               sym_tiles)
+    from ntxent_amd.parallel.symmetric import (sym_forward_bufs, sym_grad_slabs, sym_lse, sym_norm_bwd,
+                                               sym_partner_contribs, sym_step)
 
     C = _ext.load(build_if_missing=False)
     dev = torch.device("cuda", 0)
@@ -73,28 +73,19 @@ def main():
                 slabs = C.dz(cb, zqt_all, plan)
                 return C.norm_bwd(slabs, h, inv, go, plan)
 
-            tiles, nt = sym_tiles(C, plan, dev)
+            S, sp = sym_step(C, plan, dev)
 
             def symmetric_step():
-                _, inv, ypos, _ = C.prep(h, plan, zq)
-                C.transpose(zq, plan, zqt_all[r])
-                part = torch.empty((plan.col_tiles, Rpad, 2), dtype=torch.float32, device=dev)
-                part_x = torch.empty_like(part)
-                sc = torch.empty((nt * 65536,), dtype=cdt, device=dev)
-                C.fwd_stats_sym(zq, zq_all, tiles, plan, part, part_x, sc, 0, nt)
-                part.fill_(1.0)  # stands in for the received column partials (finite LSE inputs)
-                lse2 = torch.zeros((W * Rpad,), dtype=torch.float32, device=dev)
-                cpos = torch.empty((Rpad,), dtype=torch.float32, device=dev)
-                C.lse(part, ypos, lse2, cpos, plan)
-                cbuf, mbuf = sym_coef(C, plan, W, tiles, sc, lse2, cpos)
-                del sc
-                own, recv, views = sym_grad_slabs(plan, W, r, dev)
-                outs = list(sym_partner_grads(C, plan, W, r, mbuf, zqt_all).values())
-                sym_own_grad(C, plan, W, r, cbuf, zqt_all, own[0])
-                for v, o in zip(views.values(), outs):  # stands in for the received contributions
-                    if v.shape == o.shape:
-                        v.copy_(o)
-                return sym_norm_bwd(C, plan, own, recv, h, inv, go)
+                B = sym_forward_bufs(sp, plan, h, zq_all, zqt_all)
+                S.prep(plan, B)
+                S.fwd_tiles_range(plan, B, 0, sp["n_fwd"])
+                B["part"].fill_(1.0)  # stands in for the received column partials (finite LSE inputs)
+                sym_lse(S, plan, B, torch.zeros((W * Rpad,), dtype=torch.float32, device=dev))
+                sym_partner_contribs(S, sp, plan, B)
+                B["own"], recv = sym_grad_slabs(sp, plan, dev)
+                S.own_grads(plan, B)
+                recv.fill_(0.0)  # stands in for the received contributions
+                return sym_norm_bwd(S, plan, B["own"], recv, h, B["inv"], go)
 
             row = {"W": W, "rank": r, "batch": a.batch, "dim": d}
             modes = [("allgather", allgather_step)] + ([("symmetric", symmetric_step)] if W > 1 else [])
