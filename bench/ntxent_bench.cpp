@@ -236,6 +236,42 @@ class Bench {
   float loss() { return e_->loss(s_); }
   float temperature_grad() { return e_->temperature_grad(s_); }
 
+  // Engine::positive_rank (row prologue + rank kernel) timed with hipEvents; also returns the
+  // top-1 accuracy of the synthetic views through `top1`
+  std::vector<float> time_pos_rank(int warmup, int iters, double* top1) {
+    const int R = e_->geometry().rows;
+    int* rank = nullptr;
+    float *pos = nullptr, *hard = nullptr;
+    NTXENT_HIP_CHECK(hipMalloc(&rank, (size_t)R * 4));
+    NTXENT_HIP_CHECK(hipMalloc(&pos, (size_t)R * 4));
+    NTXENT_HIP_CHECK(hipMalloc(&hard, (size_t)R * 4));
+    hipEvent_t a, b;
+    NTXENT_HIP_CHECK(hipEventCreate(&a));
+    NTXENT_HIP_CHECK(hipEventCreate(&b));
+    for (int i = 0; i < warmup + 1; ++i) e_->positive_rank(h_, rank, pos, hard, s_);
+    std::vector<float> out;
+    for (int i = 0; i < iters; ++i) {
+      NTXENT_HIP_CHECK(hipEventRecord(a, s_));
+      e_->positive_rank(h_, rank, pos, hard, s_);
+      NTXENT_HIP_CHECK(hipEventRecord(b, s_));
+      NTXENT_HIP_CHECK(hipEventSynchronize(b));
+      float ms = 0;
+      NTXENT_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
+      out.push_back(ms);
+    }
+    std::vector<int> hr(R);
+    NTXENT_HIP_CHECK(hipMemcpy(hr.data(), rank, (size_t)R * 4, hipMemcpyDeviceToHost));
+    long zero = 0;
+    for (int v : hr) zero += v == 0;
+    *top1 = (double)zero / R;
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    hipFree(rank);
+    hipFree(pos);
+    hipFree(hard);
+    return out;
+  }
+
   // host fp64 NT-Xent of the same inputs (small shapes, world 1 only)
   double host_loss() const {
     const Geometry& g = e_->geometry();
@@ -297,6 +333,7 @@ struct Options {
   float T = 0.07f;
   bool check = false, graph = false, recompute = false, small = true, grad_digest = false;
   bool temperature_grad = false;  // world 1: the step also produces dL/dtau (one more small launch)
+  bool pos_rank = false;          // world 1: also time Engine::positive_rank after the usual runs
   int small_splits = 0;
   Negatives negatives = Negatives::kSymmetric;
   bool emulate = false;  // --gpus N as N emulated ranks on GPU 0 (ThreadComm), not N GPUs over RCCL
@@ -428,6 +465,7 @@ int main(int argc, char** argv) {
     else if (a == "--recompute") o.recompute = true;
     else if (a == "--no-small") o.small = false;
     else if (a == "--temperature-grad") o.temperature_grad = true;
+    else if (a == "--pos-rank") o.pos_rank = true;
     else if (a == "--fp8-bwd") ntxent::set_fp8_backward(true);
     else if (a == "--no-fp8-bwd") ntxent::set_fp8_backward(false);
     else if (a == "--no-raw-fwd") ntxent::set_raw_forward(false);
@@ -454,6 +492,7 @@ int main(int argc, char** argv) {
                   "  --no-raw-fwd: unit-row (zq) forward operands instead of the input rows normalised in the epilogue\n"
                   "  --small-fuse-rows R: small forward with the row prologue fused up to R rows (0: prep launch)\n"
                   "  --temperature-grad: time the step with the temperature gradient on (one GPU; prints dL/dtau)\n"
+                  "  --pos-rank: after the usual runs, time Engine::positive_rank (contrastive metrics; prints pos_rank_ms)\n"
                   "  --grad-digest: print a hash of dh after one step (build variants must match bitwise)\n"
                   "  (the measured A/B alternatives of earlier rounds are deleted; build-time variants:\n"
                   "   tools/build_variant.sh)\n");
@@ -511,6 +550,12 @@ int main(int argc, char** argv) {
       first = false;
     }
     if (o.temperature_grad) std::printf("       temperature grad: dL/dtau %.9e\n", bench.temperature_grad());
+    if (o.pos_rank) {
+      double top1 = 0;
+      const Result pr = stats(bench.time_pos_rank(o.warmup, o.iters, &top1));
+      std::printf("       pos_rank_ms: %.4f (std %.4f min %.4f max %.4f), top1 %.4f\n", pr.mean, pr.stdev, pr.mn, pr.mx,
+                  top1);
+    }
     if (o.grad_digest) {
       const auto gd = bench.grad_digest();
       std::printf("       grad digest: %016llx l1 %.9e loss %.6f\n", gd.first, gd.second, bench.loss());

@@ -12,7 +12,9 @@ from .ops import (  # noqa: F401,E402
     backward,
     check_matrix_core_support,
     check_tensor_core_support,
+    contrastive_metrics,
     forward,
     forward_with_stats,
     ntxent_loss,
+    positive_rank,
 )

@@ -100,6 +100,15 @@ class Engine : private StepComm {
   const float* temperature_grad_device() const { return dtau_; }
   float temperature_grad(hipStream_t stream);  // synchronises `stream`
 
+  // Contrastive metrics of this rank's own rows h ([rows][dim], input dtype), asynchronous on
+  // `stream`: the row prologue (launch_prep) and launch_pos_rank, d_rank / d_pos / d_hard being
+  // device [rows] outputs (see launch_pos_rank). Rows are normalised in the engine's backward dtype
+  // (an fp8 engine: fp16). At world > 1 the negatives are the rank-local rows only. Opt-in and
+  // outside the step: it runs out of a block of its own, allocated by the first call (the step's
+  // arena, device_bytes() and a captured graph are untouched), so it may be called at any point,
+  // also between forward() and backward().
+  void positive_rank(const void* d_h, int* d_rank, float* d_pos, float* d_hard, hipStream_t stream);
+
   float loss(hipStream_t stream);  // synchronises `stream`
   const float* loss_device() const { return loss_; }
   const float* lse2_device() const { return lse2_all_; }  // [W*Rpad] (small path: small_rows_pad), log2 units
@@ -165,6 +174,7 @@ class Engine : private StepComm {
   float* q8_lmin_ = nullptr;
   char* zq8t_ = nullptr;       // e4m3(256 Zq^T) [dim_n][q8_ldt]
   void* small_scratch_ = nullptr;
+  void* rank_buf_ = nullptr;   // positive_rank: zq [rows_pad][ld_k] | inv [rows] | ypos [rows]
   DType bwd_ = DType::F16;
   void* arena_ = nullptr;
   size_t arena_bytes_ = 0;

@@ -425,6 +425,21 @@ void launch_small_bwd(DType in, DType comp, const void* zq, const void* h, const
 // dot_out (optional, [R]): each row's z_i . g_i, stored by the block that runs the row's epilogue
 // (with column splits: the last arriver).
 
+// ---- contrastive metrics (kernels/rank_kernels.hip) --------------------------------------
+// Rank of every row's positive among its negatives, on one rank's rows (g.world == 1; g's
+// temperature plays no part). zq: launch_prep's unit rows [rows_pad][ld_k] in `comp` (fp32, fp16
+// or bf16; zero K padding and zero pad rows). With p(i) = (i + R/2) mod R and cos_ij the fp32
+// MFMA dot of rows i and j:
+//   pos_cos[i]      = <zq_i, zq_p(i)>
+//   rank[i]         = #{ j < R : j != i, j != p(i), cos_ij > pos_cos[i] }      (0: the positive wins)
+//   hard_neg_cos[i] = max of cos_ij over the same j (-inf when R == 2)
+// A similarity GEMM over the upper-triangular 128 x 128 tiles whose epilogue compares and counts:
+// no N^2 data is stored. The three outputs ([R] each) need no initialisation; counts and maxima
+// are merged with integer atomics only, so the result is bitwise repeatable. Three launches, no
+// scratch, no host sync: capturable. Opt-in: nothing in the training step calls it.
+void launch_pos_rank(DType comp, const void* zq, const Geometry& g, int* rank, float* pos_cos, float* hard_neg_cos,
+                     hipStream_t stream);
+
 // ---- device utilities (reference utils::get_optimal_block_size / check_tensor_core_support
 //      at include/ntxent_kernel.cuh:80-110) ------------------------------------------------
 struct DeviceInfo {

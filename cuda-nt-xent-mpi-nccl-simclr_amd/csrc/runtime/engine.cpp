@@ -140,6 +140,7 @@ Engine::~Engine() {
   if (ev_zq_) hipEventDestroy(ev_zq_);
   if (ev_zqt_) hipEventDestroy(ev_zqt_);
   if (comm_stream_) hipStreamDestroy(comm_stream_);
+  if (rank_buf_) hipFree(rank_buf_);
   if (arena_) hipFree(arena_);
 }
 
@@ -233,6 +234,19 @@ void Engine::before_dz(hipStream_t s) {
   if (!zqt_pending_) return;
   NTXENT_HIP_CHECK(hipStreamWaitEvent(s, ev_zqt_, 0));
   zqt_pending_ = false;
+}
+
+void Engine::positive_rank(const void* d_h, int* d_rank, float* d_pos, float* d_hard, hipStream_t s) {
+  NTXENT_TRACE("ntxent.positive_rank");
+  // this rank's rows alone, at temperature 1 (the rank does not depend on it)
+  const Geometry g = make_geometry(cfg_.rows, cfg_.dim, 1, 0, 1.0f);
+  const size_t zq_bytes = align_up((size_t)g.rows_pad * g.ld_k * cs_), row_bytes = align_up((size_t)g.rows * 4);
+  if (!rank_buf_) NTXENT_HIP_CHECK(hipMalloc(&rank_buf_, zq_bytes + 2 * row_bytes));
+  char* base = static_cast<char*>(rank_buf_);
+  float* inv = reinterpret_cast<float*>(base + zq_bytes);
+  float* ypos = reinterpret_cast<float*>(base + zq_bytes + row_bytes);
+  launch_prep(cfg_.input, bwd_, d_h, base, inv, ypos, g, s);
+  launch_pos_rank(bwd_, base, g, d_rank, d_pos, d_hard, s);
 }
 
 void Engine::set_temperature(float temperature) {

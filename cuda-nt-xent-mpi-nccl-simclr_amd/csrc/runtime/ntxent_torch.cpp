@@ -248,6 +248,36 @@ std::vector<at::Tensor> prep(const at::Tensor& h, const Plan& P, const c10::opti
   return {zq, inv, ypos, zq8};
 }
 
+// Contrastive metrics, stage level: zq = prep's unit rows of a world-1 plan (its temperature plays
+// no part). Returns {rank int32 [R], pos_cos fp32 [R], hard_neg_cos fp32 [R]} (launch_pos_rank).
+std::vector<at::Tensor> pos_rank(const at::Tensor& zq, const Plan& P) {
+  check_input(zq, "zq");
+  NTXENT_CHECK(P.g.world == 1, "pos_rank: one rank only (a plan with world == 1)");
+  NTXENT_CHECK(zq.numel() == (long)P.g.rows_pad * P.g.ld_k && zq.scalar_type() == to_scalar(P.bwd()),
+               "zq must be [rows_pad, ld_k] in the plan's backward dtype");
+  const at::DeviceGuard guard(zq.device());
+  auto rank = at::empty({P.g.rows}, opts(zq, at::kInt));
+  auto pos = at::empty({P.g.rows}, opts(zq, at::kFloat));
+  auto hard = at::empty({P.g.rows}, opts(zq, at::kFloat));
+  launch_pos_rank(P.bwd(), zq.data_ptr(), P.g, rank.data_ptr<int>(), pos.data_ptr<float>(), hard.data_ptr<float>(),
+                  cur_stream(zq));
+  return {rank, pos, hard};
+}
+
+// Contrastive metrics of stacked views h = [h1; h2] on the current stream: the row prologue and
+// pos_rank. The compute dtype resolves as choose_compute does; "fp8" computes in fp16 (the rank
+// kernel has no fp8 operands).
+std::vector<at::Tensor> positive_rank(const at::Tensor& h, const std::string& compute, bool use_mixed_precision) {
+  check_input(h, "h");
+  NTXENT_CHECK(h.dim() == 2, "h must be 2-D [2N, d]");
+  NTXENT_CHECK(h.size(0) > 0 && h.size(0) % 2 == 0, "h must hold an even number of rows (two stacked views)");
+  const at::DeviceGuard guard(h.device());
+  const DType comp = backward_dtype(choose_compute(h.scalar_type(), use_mixed_precision, compute));
+  auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, 1.0, dtype_name(comp), h.device().index());
+  const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
+  return pos_rank(st[0], *P);
+}
+
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {
   check_input(zq, "zq");
   const at::DeviceGuard guard(zq.device());
@@ -1051,6 +1081,17 @@ class NativeEngine {
     NTXENT_HIP_CHECK(hipMemcpyAsync(out.data_ptr(), src, sizeof(float), hipMemcpyDeviceToDevice, cur_stream(h_)));
     return out;
   }
+  // Engine::positive_rank of this rank's rows h: {rank, pos_cos, hard_neg_cos}
+  std::vector<at::Tensor> positive_rank(const at::Tensor& h) {
+    check_h(h);
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(device_);
+    auto rank = at::empty({h.size(0)}, h.options().dtype(at::kInt));
+    auto pos = at::empty({h.size(0)}, h.options().dtype(at::kFloat));
+    auto hard = at::empty({h.size(0)}, h.options().dtype(at::kFloat));
+    eng_->positive_rank(h.data_ptr(), rank.data_ptr<int>(), pos.data_ptr<float>(), hard.data_ptr<float>(),
+                        cur_stream(h));
+    return {rank, pos, hard};
+  }
   size_t device_bytes() const { return eng_->device_bytes(); }
   bool symmetric() const { return eng_->symmetric(); }
   bool small() const { return eng_->small(); }
@@ -1150,6 +1191,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("replay", &NativeEngine::replay)
       .def("set_temperature", &NativeEngine::set_temperature, py::arg("temperature"))
       .def("temperature_grad", &NativeEngine::temperature_grad)
+      .def("positive_rank", &NativeEngine::positive_rank, py::arg("h"))
       .def_property_readonly("temperature", &NativeEngine::temperature)
       .def_property_readonly("captured", &NativeEngine::captured)
       .def_property_readonly("device_bytes", &NativeEngine::device_bytes)
@@ -1166,6 +1208,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("prep", &prep, py::arg("h"), py::arg("plan"), py::arg("zq_out") = py::none(), py::arg("zq8_out") = py::none());
   m.def("transpose", &transpose, py::arg("zq"), py::arg("plan"), py::arg("zqt_out") = py::none());
+  m.def("pos_rank", &pos_rank, py::arg("zq"), py::arg("plan"),
+        "Stage op: (rank, pos_cos, hard_neg_cos) of prep's unit rows zq for a world-1 plan.");
+  m.def("positive_rank", &positive_rank, py::arg("h"), py::arg("compute") = "auto",
+        py::arg("use_mixed_precision") = false,
+        "(rank, pos_cos, hard_neg_cos) of stacked views h = [h1; h2] on the current stream: rank[i] counts the "
+        "negatives whose cosine is strictly larger than the positive's. compute: auto|fp32|fp16|bf16|fp8, "
+        "resolved as for the loss; fp8 computes in fp16.");
   m.def("fwd_stats_range", &fwd_stats_range, py::arg("zq_local"), py::arg("zq_all"), py::arg("plan"), py::arg("part"),
         py::arg("sc"), py::arg("first"), py::arg("count"), py::arg("reserve_cus") = 0);
   m.def("fwd_stats", [](const at::Tensor& zl, const at::Tensor& za, const Plan& P, bool keep) {

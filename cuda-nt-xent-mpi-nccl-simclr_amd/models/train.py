@@ -2,6 +2,7 @@
 
   python -m ntxent_amd.models.train --steps 50 --batch 256
   python -m ntxent_amd.models.train --steps 50 --batch 256 --learnable-temperature true   # one GPU
+  python -m ntxent_amd.models.train --steps 50 --batch 256 --metrics-every 10   # top-1 / top-5 every 10 steps
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
       -m ntxent_amd.models.train --steps 200 --batch 512 --ckpt-dir ckpt/ --ckpt-every 50
 """

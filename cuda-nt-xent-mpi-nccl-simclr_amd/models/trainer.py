@@ -68,6 +68,11 @@ class TrainConfig:
     resume: bool = True
     log_every: int = 10
     metrics_path: Optional[str] = None
+    # > 0: on steps where step % metrics_every == 0 the record also carries the contrastive metrics
+    # of the step's embeddings (top1, top5, mean_rank, pos_cos, hard_neg_cos, negatives;
+    # NTXentLoss.metrics). One extra launch sequence after the step, outside step_ms. With several
+    # ranks each rank ranks its own 2 x batch rows only (negatives = 2 x batch - 2).
+    metrics_every: int = 0
 
 
 def _dist():
@@ -203,6 +208,10 @@ class SimCLRTrainer:
                "images_per_s": cfg.batch * self.world / dt}
         if cfg.learnable_temperature:  # the temperature the next step uses
             rec["temperature"] = float(self.loss_fn.current_temperature().detach())
+        if cfg.metrics_every > 0 and self.step % cfg.metrics_every == 0:
+            with trace_range("simclr.metrics"):
+                m = self.loss_fn.metrics(z.detach(), topk=(1, 5))
+            rec.update({k: (int(v) if k == "negatives" else float(v)) for k, v in m.items()})
         if not math.isfinite(lv):
             raise FloatingPointError(f"non-finite loss at step {self.step}")
         self.step += 1
@@ -213,6 +222,8 @@ class SimCLRTrainer:
                 extra["log_temperature"] = float(self.loss_fn.log_temperature.detach())
             else:  # option off: the checkpoint is what it was before the option existed
                 del conf["learnable_temperature"]
+            if not cfg.metrics_every:
+                del conf["metrics_every"]
             save_checkpoint(Path(cfg.ckpt_dir) / f"ckpt_{self.step}.pt", model=self.model, optimizer=self.opt,
                             step=self.step, extra=extra, rank=self.rank)
         return rec

@@ -188,6 +188,17 @@ class NTXentLoss(torch.nn.Module):
         return ntxent_loss(h, self.current_temperature(), use_mixed_precision=self.use_mixed_precision,
                            compute=self.compute, keep_logits=self.keep_logits)
 
+    def metrics(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None, topk=(1, 5)):
+        """Contrastive metrics of the same inputs ``forward`` takes (``ops.metrics.contrastive_metrics``:
+        ``top{k}``, ``mean_rank``, ``pos_cos``, ``hard_neg_cos``, ``negatives``) with the module's
+        ``compute`` and ``use_mixed_precision``; no gradient, and independent of the temperature.
+        A distributed module ranks each row against this rank's own ``2n`` rows only
+        (``negatives = 2n - 2``), not against the global batch."""
+        from .metrics import contrastive_metrics
+
+        return contrastive_metrics(z1, z2=z2, topk=topk, compute=self.compute,
+                                   use_mixed_precision=self.use_mixed_precision)
+
     def extra_repr(self) -> str:
         s = f"temperature={self.temperature}, compute={self.compute}, distributed={self.distributed}"
         if self.learnable_temperature:

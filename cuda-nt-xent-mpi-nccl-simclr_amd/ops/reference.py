@@ -100,6 +100,52 @@ def ntxent_temperature_grad_analytic(h: torch.Tensor, temperature: float,
 
 
 # ---------------------------------------------------------------------------------------
+# Contrastive metrics: the rank of each row's positive among its negatives.
+# ---------------------------------------------------------------------------------------
+def _negatives_mask(rows: int, device=None) -> torch.Tensor:
+    """[R, R] bool: True where column j is a negative of row i (j != i and j != p(i))."""
+    idx = torch.arange(rows, device=device)
+    keep = torch.ones(rows, rows, dtype=torch.bool, device=device)
+    keep[idx, idx] = False
+    keep[idx, positive_index(rows, device)] = False
+    return keep
+
+
+def _rank_parts(z_unit: torch.Tensor, delta: float):
+    """(lo, hi, t, hard) of unit rows: negatives with cos > t + delta / cos > t - delta, the positive
+    cosine t and the largest negative cosine (-inf without negatives)."""
+    if z_unit.dim() != 2 or z_unit.shape[0] % 2:
+        raise ValueError("expected stacked views [2N, d]")
+    R = z_unit.shape[0]
+    cos = z_unit @ z_unit.t()
+    t = cos.gather(1, positive_index(R, z_unit.device).unsqueeze(1))
+    keep = _negatives_mask(R, z_unit.device)
+    lo = ((cos > t + delta) & keep).sum(1)
+    hi = ((cos > t - delta) & keep).sum(1)
+    hard = cos.masked_fill(~keep, float("-inf")).max(1).values
+    return lo, hi, t.squeeze(1), hard
+
+
+def positive_rank_bounds(z_unit: torch.Tensor, delta: float):
+    """(lo, hi) for unit rows ``z_unit`` ([2N, d], used as they are): ``lo`` counts the negatives
+    with ``cos > t + delta`` and ``hi`` those with ``cos > t - delta``, t being the positive cosine.
+    An implementation whose cosines are all within ``delta / 2`` of these has ``lo <= rank <= hi``."""
+    lo, hi, _, _ = _rank_parts(z_unit, delta)
+    return lo, hi
+
+
+def positive_rank(h: torch.Tensor):
+    """(rank int32 [2N], pos_cos [2N], hard_neg_cos [2N]) of stacked views ``h = [h1; h2]``, in the
+    dtype of ``h``: rank_i = #{ j : j != i, j != p(i), cos_ij > cos_i,p(i) } (strict), so 0 means
+    the positive is the most similar row. hard_neg_cos is -inf when there are no negatives."""
+    if h.dim() != 2 or h.shape[0] % 2:
+        raise ValueError("expected stacked views [2N, d]")
+    z, _ = normalize(h)
+    lo, _, t, hard = _rank_parts(z, 0.0)
+    return lo.to(torch.int32), t, hard
+
+
+# ---------------------------------------------------------------------------------------
 # Data-parallel layout: rank r holds h_r = [h1_r; h2_r] (2n rows); positives are rank-local.
 # ---------------------------------------------------------------------------------------
 def global_pair_order(shards: Sequence[torch.Tensor]) -> torch.Tensor:

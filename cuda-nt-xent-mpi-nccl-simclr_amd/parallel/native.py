@@ -105,6 +105,11 @@ class NativeNTXent:
         a 0-d fp32 tensor; needs ``temperature_grad=True`` at construction."""
         return self._e.temperature_grad()
 
+    def positive_rank(self, h: torch.Tensor):
+        """``(rank, pos_cos, hard_neg_cos)`` of this rank's rows ``h`` (``ops.metrics.positive_rank``)
+        from the engine's own buffers; opt-in, outside the step, callable at any point."""
+        return tuple(self._e.positive_rank(self._check(h)))
+
     @property
     def captured(self) -> bool:
         return self._e.captured
