@@ -7,6 +7,8 @@ trainer), ``utils`` (device checks, memory tracking, timing).
 __version__ = "0.1.0"
 
 from .ops import (  # noqa: F401,E402
+    InfoNCEFunction,
+    InfoNCELoss,
     NTXentFunction,
     NTXentLoss,
     backward,
@@ -15,6 +17,7 @@ from .ops import (  # noqa: F401,E402
     contrastive_metrics,
     forward,
     forward_with_stats,
+    info_nce_loss,
     ntxent_loss,
     positive_rank,
 )

@@ -440,6 +440,40 @@ void launch_small_bwd(DType in, DType comp, const void* zq, const void* h, const
 void launch_pos_rank(DType comp, const void* zq, const Geometry& g, int* rank, float* pos_cos, float* hard_neg_cos,
                      hipStream_t stream);
 
+// ---- cross-view InfoNCE (kernels/xview_kernels.hip) --------------------------------------
+// The CLIP-form two-tower loss of one rank's rows (g.world == 1): a row's columns are the rows of
+// the OTHER view only, the positive p(i) = (i + R/2) mod R included,
+//   loss = 1/R sum_i (lse_i - cos_ip / tau),  lse_i = log sum_{j : view(j) != view(i)} exp(cos_ij / tau).
+// zq: launch_prep's unit rows [rows_pad][ld_k] in `comp` (fp32, fp16 or bf16). Only the N x N block
+// Z1 Z2^T is computed (128 x 128 MFMA tiles). ypos ([>= N] floats, e.g. launch_prep's): the forward
+// WRITES the pairs' positive logits there, taken from the diagonal of the block, so that a pair's
+// positive and its negatives come from the same MFMA sums (whatever it held is overwritten).
+//
+// Forward: the tile epilogue writes negatives-only (max, sum exp2) partials of the view-1 rows and
+// the view-2 rows (launch_lse's `part` layout) into `scratch` (xview_fwd_scratch_bytes, 8-byte
+// aligned, no initialisation needed); a merge launch gives lse2 / cpos ([rows_pad] each, with
+// launch_lse's meaning) and the pairs' loss terms, a one-block launch their fixed-order sum: loss[0].
+// Three launches, deterministic, no atomics.
+size_t xview_fwd_scratch_bytes(const Geometry& g);
+void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g, float* lse2, float* cpos,
+                      float* loss, void* scratch, hipStream_t stream);
+// Backward, two stages followed by launch_norm_bwd (fp32 slab, dot_out) and, for dL/dtau,
+// launch_tau_grad; between the stages the caller may release zq, after the second coef and zt:
+//   launch_xview_coef: both views' transposed rows into `zt` (xview_zt_bytes) and the coefficient
+//     block G = P12 + P21^T - 2 I into `coef` (xview_coef_bytes), written once: one fp32 plane for
+//     fp32 plans; for 16-bit plans two planes in the compute dtype, G rounded to it and the scaled
+//     residual of that rounding, so the MFMA operands carry about twice the dtype's mantissa.
+//     4 N_pad^2 bytes in every plan: the only N^2 data.
+//   launch_xview_dz: G Z2, G -> G^T in place in `coef`, then G^T Z1, on MFMA into the fp32 slab
+//     `dz` (xview_dz_bytes: [rows_pad][dim_n], rows < R and columns < roundup(dim_k, 128) written).
+// No buffer needs initialisation; no host sync, no atomics: deterministic and capturable.
+size_t xview_coef_bytes(DType comp, const Geometry& g);
+size_t xview_zt_bytes(DType comp, const Geometry& g);
+size_t xview_dz_bytes(const Geometry& g);
+void launch_xview_coef(DType comp, const void* zq, const float* lse2, const float* cpos, const Geometry& g, void* coef,
+                       void* zt, hipStream_t stream);
+void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream);
+
 // ---- device utilities (reference utils::get_optimal_block_size / check_tensor_core_support
 //      at include/ntxent_kernel.cuh:80-110) ------------------------------------------------
 struct DeviceInfo {

@@ -1,0 +1,639 @@
+// Cross-view InfoNCE kernels for gfx950: the CLIP-form two-tower loss of one rank's rows.
+//
+// Rows are stacked as everywhere else (zq = launch_prep's unit rows, R = 2N, p(i) = (i + N) mod R),
+// but a row's columns are the rows of the OTHER view only, the positive included:
+//   lse_i = log sum_{j : view(j) != view(i)} exp(cos_ij / tau),  loss = 1/R sum_i (lse_i - cos_ip / tau)
+// Only the N x N block S12 = Z1 Z2^T is ever needed: its rows are the view-1 rows' logits and its
+// columns the view-2 rows'. With P_ij = exp(cos_ij / tau - lse_i) the gradient block is
+//   G = P12 + P21^T - 2 I      (N x N; the diagonal, the positives, is the merge's cpos)
+// and (C z)[0:N] = G Z2, (C z)[N:] = G^T Z1.
+//
+//   xview_fwd_kernel  : one 128 x 128 tile of S12 per workgroup, all nT x nT tiles (no symmetry
+//                       in this block). The MFMA loop is rank_kernels.hip's (4 waves of 64 x 64,
+//                       LDS-DMA double buffer, XOR-swizzled image). Epilogue: negatives-only
+//                       (max, sum exp2) per row for the view-1 rows and per column for the view-2
+//                       rows, reduced in the wave and across the two waves in a fixed order, and
+//                       stored in launch_lse's `part` layout: slot J for the rows, slot I for the
+//                       columns (nT = rows_pad / 256 slots: exactly launch_lse's column tiles).
+//                       Every (slot, row < R) is written exactly once; the diagonal tiles also
+//                       store the pairs' positive logits (ypos), so a pair's positive and its
+//                       negatives come from the same MFMA arithmetic.
+//   xview_lse_kernel  : a thread per positive pair merges the slots of both rows in slot order with
+//                       the positive logit (negatives-only LSE merged with y_pos and the positive
+//                       coefficient -(sigmoid(lse_neg_i - y) + sigmoid(lse_neg_p - y)), as launch_lse:
+//                       stable when P_ip -> 1); the loss terms are formed in fp64 relative to y_pos.
+//   xview_loss_kernel : their sum in a fixed order (one block, fp64 tree). No atomics anywhere.
+//   xview_coef_kernel : the same tile GEMM again; the epilogue forms the tile of G from lse2 / cpos
+//                       and stores it once, row-major [N_pad][N_pad] planes in the compute dtype
+//                       (zeros outside N x N): one fp32 plane, or for 16-bit plans G rounded to the
+//                       dtype and the scaled residual of that rounding, so that the MFMA operands
+//                       carry the coefficients to about twice the dtype's mantissa (a gradient of
+//                       equal coefficients is otherwise off by the dtype's rounding of that one
+//                       number). The only N^2 data, 4 N_pad^2 bytes in every plan.
+//   xview_transpose_kernel : Zt[v][e][c] = zq[v N + c][e], both views aligned at column 0 and zero
+//                       padded to N_pad columns and roundup(dim_k, 128) rows (view 2 starts at row
+//                       N of zq, which is usually not tile aligned).
+//   xview_dz_kernel   : out = G Z2, and after xview_gt_kernel has transposed the planes in place,
+//                       G^T Z1: one 128 x 128 output tile per workgroup, K = N_pad, both operands
+//                       streamed K-major by LDS-DMA in the same MFMA loop; 16-bit plans run the
+//                       residual plane, scale the accumulators back and run the hi plane. fp32
+//                       output slab. Each output element is one workgroup's fixed-order sum:
+//                       deterministic.
+// launch_norm_bwd (with dot_out) and launch_tau_grad finish the backward as they are.
+#include "../include/ntxent/ntxent.h"
+#include "device_common.h"
+
+namespace ntxent {
+namespace dev {
+
+constexpr int kXvTile = 128;
+constexpr int kXvThreads = 256;
+constexpr int kXvStage = kXvTile * kKStepBytes;  // LDS bytes of one operand's K-step (16 KiB)
+
+struct XvParams {
+  const char* zq;   // [rows_pad][ldb bytes] unit rows (zero K padding, zero pad rows)
+  long long ldb;    // row stride in bytes
+  int n_half;       // N
+  int rows_pad;
+  int nk;           // 128-byte K-steps per row of zq
+  int nT;           // 128-row tiles per side of the N x N block
+  float scale2;     // log2(e) / tau: cosine -> logit in log2 units
+  float2* part;     // forward: [nT][rows_pad] (launch_lse's layout)
+  float* ypos;      // forward: [>= N] positive logits of the pairs (log2 units), written
+  const float* lse2;  // coefficient pass: [rows_pad] LSE (log2 units, positive included)
+  const float* cpos;  //                   [rows_pad] positive coefficient
+  char* gbuf;       // [planes][N_pad][ldg bytes] G in the compute dtype (16-bit: residual plane, hi plane)
+  long long ldg;
+  long long plane_bytes;
+};
+// 16-bit plans: the residual plane holds (G - hi) * kXvLoScale, clear of fp16's subnormals; the dZ
+// runs it first and scales its accumulators back (a power of two: exact) before the hi plane.
+constexpr float kXvLoScale = 2048.f;
+
+// LDS image of a [128 rows][128 B] K-step: 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7)
+// (rank_kernels.hip: conflict-free ds_read_b128 of 16 rows x one chunk).
+__device__ __forceinline__ int xv_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+
+// Stage K-step bytes [0, 128) of 128 rows starting at `src` (rows ld apart) into `dst`: every wave
+// moves 4 pieces of 1 KiB (8 rows); LDS is written lane-linear, the swizzle is applied on the source
+// address.
+__device__ __forceinline__ void xv_stage(const char* src, long long ld, lds_char* dst, int w, int lane) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int piece = w * 4 + q;
+    const int row = piece * 8 + (lane >> 3);
+    const int lc = (lane & 7) ^ ((row >> 1) & 7);
+    __builtin_amdgcn_global_load_lds((const void*)(src + (long long)row * ld + lc * 16),
+                                     (lds_void*)(dst + piece * 1024), 16, 0, 0);
+  }
+}
+
+// One K-step of the 128 x 128 tile from the staged images: 4 x 4 MFMA blocks of 16 x 16 per wave.
+template <typename T>
+__device__ __forceinline__ void xv_mma_step(const lds_char* aimg, const lds_char* bimg, int wr, int wc, int r16, int g,
+                                            f32x4 (&acc)[4][4]) {
+  typedef typename Mfma<T>::frag frag;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    frag a[4], bf[4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+      a[mi] = *(__attribute__((address_space(3))) const frag*)(aimg + xv_off(64 * wr + 16 * mi + r16, 4 * ks + g));
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+      bf[ni] = *(__attribute__((address_space(3))) const frag*)(bimg + xv_off(64 * wc + 16 * ni + r16, 4 * ks + g));
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Mfma<T>::mma(a[mi], bf[ni], acc[mi][ni]);
+  }
+}
+
+// acc = tile (I, J) of Z1 Z2^T: rows I * 128 .. of zq against rows N + J * 128 .. of zq. Ends with a
+// block barrier: the caller's epilogue may reuse the staging images.
+template <typename T>
+__device__ __forceinline__ void xv_tile_gemm(const XvParams& p, int I, int J, lds_char* lds, int w, int lane,
+                                             f32x4 (&acc)[4][4]) {
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const char* arow = p.zq + (long long)I * kXvTile * p.ldb;
+  const char* brow = p.zq + ((long long)p.n_half + (long long)J * kXvTile) * p.ldb;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // buffer s: A image at s * 2 * kXvStage, B image behind it
+  xv_stage(arow, p.ldb, lds, w, lane);
+  xv_stage(brow, p.ldb, lds + kXvStage, w, lane);
+  for (int k = 0; k < p.nk; ++k) {
+    // step k landed for this wave; the barrier makes it visible to every wave and orders every
+    // wave's reads of step k - 1 (lgkmcnt) before its slot is restaged
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (k + 1 < p.nk) {
+      lds_char* nxt = lds + ((k + 1) & 1) * 2 * kXvStage;
+      xv_stage(arow + (long long)(k + 1) * kKStepBytes, p.ldb, nxt, w, lane);
+      xv_stage(brow + (long long)(k + 1) * kKStepBytes, p.ldb, nxt + kXvStage, w, lane);
+    }
+    const lds_char* aimg = lds + (k & 1) * 2 * kXvStage;
+    xv_mma_step<T>(aimg, aimg + kXvStage, wr, wc, r16, g, acc);
+  }
+  __syncthreads();
+}
+
+// ---- forward: LSE partials of the tile's rows (view 1) and columns (view 2) -----------------
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p) {
+  // ONE __shared__ object (staging ring, reused by the epilogue)
+  __shared__ __attribute__((aligned(16))) char smem[4 * kXvStage];
+  lds_char* lds = (lds_char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int I = b / p.nT, J = b - I * p.nT;
+  const int N = p.n_half;
+
+  f32x4 acc[4][4];
+  xv_tile_gemm<T>(p, I, J, lds, w, lane, acc);
+
+  // epilogue LDS: per-wave-column row (max, sum) | per-wave-row column (max, sum)
+  float* s_rm = reinterpret_cast<float*>(smem);  // [2][128]
+  float* s_rs = s_rm + 2 * kXvTile;
+  float* s_cm = s_rs + 2 * kXvTile;
+  float* s_cs = s_cm + 2 * kXvTile;
+
+  int cj[4];
+  float cm[4], cs[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    cj[ni] = J * kXvTile + 64 * wc + 16 * ni + r16;
+    cm[ni] = kNegInf;
+    cs[ni] = 0.f;
+  }
+  // pass 1: logits (log2 units; -inf for what is no negative) and the maxima
+  float rmx[4][4];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int gi = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+      float m = kNegInf;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        // a view-1 tile row at or beyond N is a view-2 row and a view-2 tile row at or beyond N is a
+        // pad row (cosine 0) or nothing of this problem: masked by index. The positive (the diagonal
+        // of the block) joins in xview_lse_kernel.
+        const bool in = (gi < N) & (cj[ni] < N);
+        const bool ok = in & (cj[ni] != gi);
+        const float yv = acc[mi][ni][r] * p.scale2;
+        // the pair's positive logit from the same MFMA sum as its negatives (one lane of one tile
+        // per pair): rows whose cosines are equal then have exactly equal logits
+        if (in & (cj[ni] == gi)) p.ypos[gi] = yv;
+        const float y = ok ? yv : kNegInf;
+        acc[mi][ni][r] = y;
+        m = fmaxf(m, y);
+        cm[ni] = fmaxf(cm[ni], y);
+      }
+      rmx[mi][r] = row16_max(m);
+    }
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) cm[ni] = xrow_max(cm[ni]);
+  // pass 2: sums of exp2 against the maxima
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rt = 64 * wr + 16 * mi + 4 * g + r;
+      const float mr = rmx[mi][r];
+      float s = 0.f;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const float y = acc[mi][ni][r];
+        const bool ok = y != kNegInf;
+        s += ok ? fast_exp2(y - mr) : 0.f;
+        cs[ni] += ok ? fast_exp2(y - cm[ni]) : 0.f;
+      }
+      s = row16_sum(s);
+      if (r16 == 0) {
+        s_rm[wc * kXvTile + rt] = mr;
+        s_rs[wc * kXvTile + rt] = s;
+      }
+    }
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    cs[ni] = xrow_sum(cs[ni]);
+    if (g == 0) {
+      const int ct = 64 * wc + 16 * ni + r16;
+      s_cm[wr * kXvTile + ct] = cm[ni];
+      s_cs[wr * kXvTile + ct] = cs[ni];
+    }
+  }
+  __syncthreads();
+  // threads [0, 128): the tile's rows -> slot J; [128, 256): its columns -> slot I
+  {
+    const bool col = tid >= kXvTile;
+    const int t = tid & (kXvTile - 1);
+    const float* sm = col ? s_cm : s_rm;
+    const float* ss = col ? s_cs : s_rs;
+    float m = sm[t], s = ss[t];
+    lse_merge(m, s, sm[kXvTile + t], ss[kXvTile + t]);
+    const int idx = (col ? J : I) * kXvTile + t;  // index within the view
+    if (idx < N) {
+      const long long slot = col ? I : J;
+      p.part[slot * p.rows_pad + (col ? N + idx : idx)] = make_float2(m, s);
+    }
+  }
+}
+
+// ---- forward: merge of the partials, row statistics and the loss ---------------------------------
+// Row statistics from a row's merged negatives-only (max, sum) state and the pair's positive logit
+// (all log2 units): returns lse2 = logaddexp2(lse_neg, y_pos) and a = 1 - P_ip = sigmoid(lse_neg -
+// y_pos) as device_common.h's finish_row does; the loss term softplus(lse_neg - y_pos) is formed in
+// fp64 from (m - y_pos) + log2 s, the difference taken before the logarithm is added: both logits
+// are of size 1 / tau and their fp32 sum m + log2 s would round at that size, not at the loss's.
+__device__ __forceinline__ float xv_finish_row(float m, float s, float yp, double& loss, float& a) {
+  const bool empty = m == kNegInf || s <= 0.f;
+  const float neg2 = empty ? kNegInf : m + log2f(s);
+  const float mx = fmaxf(neg2, yp);
+  const float l2 = mx + log2f(exp2f(neg2 - mx) + exp2f(yp - mx));
+  const double x = empty ? -(double)kPosInf : (((double)m - (double)yp) + log2((double)s)) * 0.6931471805599453;
+  loss = x > 0.0 ? x + log1p(exp(-x)) : log1p(exp(x));
+  a = (float)(1.0 / (1.0 + exp(-x)));
+  return l2;
+}
+
+// One thread per positive pair (i, i + N): the nT slots of both rows merged in slot order, then
+// lse2 / cpos of both rows and the pair's loss terms (lpair, fp64). The threads behind the pairs
+// zero the pad rows [R, rows_pad) of lse2 / cpos.
+__global__ __launch_bounds__(256) void xview_lse_kernel(const float2* __restrict__ part, const float* __restrict__ ypos,
+                                                        float* __restrict__ lse2, float* __restrict__ cpos,
+                                                        double* __restrict__ lpair, int N, int rows_pad, int nT) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < N) {
+    float mi = kNegInf, si = 0.f, mj = kNegInf, sj = 0.f;
+    for (int t = 0; t < nT; ++t) {
+      const float2 a = part[(long long)t * rows_pad + i], b = part[(long long)t * rows_pad + N + i];
+      lse_merge(mi, si, a.x, a.y);
+      lse_merge(mj, sj, b.x, b.y);
+    }
+    const float yp = ypos[i];
+    double li, lj;
+    float ai, aj;
+    lse2[i] = xv_finish_row(mi, si, yp, li, ai);
+    lse2[N + i] = xv_finish_row(mj, sj, yp, lj, aj);
+    // C_ip = P_ip + P_pi - 2 = -(a_i + a_p): no 1 - P cancellation when P_ip -> 1
+    cpos[i] = -(ai + aj);
+    cpos[N + i] = -(ai + aj);
+    lpair[i] = li + lj;
+  } else if (i - N < rows_pad - 2 * N) {
+    lse2[2 * N + (i - N)] = 0.f;
+    cpos[2 * N + (i - N)] = 0.f;
+  }
+}
+
+// loss = (sum of lpair) / R. One block: thread t sums pairs t, t + 1024, ... in order, then a fixed
+// halving tree (fp64): deterministic, no atomics.
+constexpr int kXvSumThreads = 1024;
+__global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double* __restrict__ lpair, int N,
+                                                                   float* __restrict__ loss) {
+  __shared__ double red[kXvSumThreads];
+  double t = 0.0;
+  for (int i = threadIdx.x; i < N; i += kXvSumThreads) t += lpair[i];
+  red[threadIdx.x] = t;
+  __syncthreads();
+#pragma unroll
+  for (int n = kXvSumThreads / 2; n > 0; n >>= 1) {
+    if ((int)threadIdx.x < n) red[threadIdx.x] += red[threadIdx.x + n];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (2.0 * (double)N));
+}
+
+// ---- backward: the tile of G = P12 + P21^T - 2 I, stored once ---------------------------------
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * kXvStage];
+  lds_char* lds = (lds_char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int I = b / p.nT, J = b - I * p.nT;
+  const int N = p.n_half;
+
+  f32x4 acc[4][4];
+  xv_tile_gemm<T>(p, I, J, lds, w, lane, acc);
+
+  // the tile's planes in the compute dtype, row-major [128][128] each, over the staging images
+  // (64 KiB): fp32 plans one plane, G; 16-bit plans the residual plane (G - hi) * 2^11, then hi =
+  // G rounded to T. The dZ adds both, so the coefficients carry about 2 x the operand's mantissa.
+  constexpr bool kSplit = sizeof(T) == 2;
+  constexpr int kPlaneElems = kXvTile * kXvTile;
+  T* s_g = reinterpret_cast<T*>(smem);
+  int cj[4];
+  float lc[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    cj[ni] = J * kXvTile + 64 * wc + 16 * ni + r16;
+    lc[ni] = cj[ni] < N ? p.lse2[N + cj[ni]] : 0.f;
+  }
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rt = 64 * wr + 16 * mi + 4 * g + r;
+      const int gi = I * kXvTile + rt;
+      const float li = gi < N ? p.lse2[gi] : 0.f;
+      const float cp = gi < N ? p.cpos[gi] : 0.f;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const float y = acc[mi][ni][r] * p.scale2;
+        const bool ok = (gi < N) & (cj[ni] < N);
+        const float c = fast_exp2(y - li) + fast_exp2(y - lc[ni]);
+        // selects, not products: outside N x N the exponentials may overflow
+        const float v = ok ? (cj[ni] == gi ? cp : c) : 0.f;
+        const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
+        const T hi = from_f32<T>(v);
+        if constexpr (kSplit) {
+          s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
+          s_g[kPlaneElems + at] = hi;
+        } else {
+          s_g[at] = hi;
+        }
+      }
+    }
+  __syncthreads();
+  // 16-byte chunks, rows contiguous: 8 * sizeof(T) chunks per row, 4096 chunks in all
+  constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
+  constexpr int kCpp = kCpr * kXvTile;  // chunks per plane
+  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
+#pragma unroll
+  for (int q = 0; q < 4 * kXvStage / 16 / kXvThreads; ++q) {
+    const int idx = q * kXvThreads + tid;
+    const int plane = idx / kCpp, in = idx - plane * kCpp;
+    const int row = in / kCpr, cc = in - row * kCpr;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
+    *reinterpret_cast<u32x4*>(gt + plane * p.plane_bytes + (long long)row * p.ldg + cc * 16) = v;
+  }
+}
+
+// ---- Zt[v][e][c] = zq[v N + c][e] --------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void xview_transpose_kernel(const T* __restrict__ zq, T* __restrict__ zt, int N,
+                                                              int dim_k, long long ldk, int En, long long ldz) {
+  __shared__ T tile[64][65];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c0 = blockIdx.x * 64, e0 = blockIdx.y * 64, v = blockIdx.z;
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int c = c0 + ty + 4 * j, e = e0 + tx;
+    tile[ty + 4 * j][tx] = (c < N && e < dim_k) ? zq[((long long)v * N + c) * ldk + e] : from_f32<T>(0.f);
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int e = e0 + ty + 4 * j, c = c0 + tx;
+    zt[((long long)v * En + e) * ldz + c] = tile[tx][ty + 4 * j];
+  }
+}
+
+// ---- G -> G^T in place (every plane) -------------------------------------------------------------
+// One workgroup per pair of 64 x 64 tiles (bx <= by) of a square [np][np] plane: both tiles go
+// through LDS and come back transposed in each other's place (a diagonal tile in its own). No
+// element is touched by two workgroups.
+template <typename T>
+__global__ __launch_bounds__(256) void xview_gt_kernel(T* __restrict__ gbuf, long long np, long long plane_elems) {
+  const int bx = blockIdx.x, by = blockIdx.y;
+  if (bx > by) return;
+  __shared__ T ta[64][65], tb[64][65];
+  T* gp = gbuf + (long long)blockIdx.z * plane_elems;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  T* a = gp + ((long long)by * 64) * np + (long long)bx * 64;  // tile (by, bx)
+  T* b = gp + ((long long)bx * 64) * np + (long long)by * 64;  // tile (bx, by)
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int r = ty + 4 * j;
+    ta[r][tx] = a[r * np + tx];
+    tb[r][tx] = b[r * np + tx];
+  }
+  __syncthreads();
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const int r = ty + 4 * j;
+    a[r * np + tx] = tb[tx][r];
+    if (bx != by) b[r * np + tx] = ta[tx][r];
+  }
+}
+
+// ---- out = A Z^T-rows: G Z2 (side 0, A = G) | G^T Z1 (side 1, A = G^T) ----------------------------
+struct XvDzParams {
+  const char* gbuf;  // [planes][N_pad][ldg bytes]: G, or G^T after xview_gt_kernel
+  long long ldg;
+  long long plane_bytes;
+  int planes;        // 1, or 2: the residual plane (scaled by kXvLoScale), then the hi plane
+  const char* zt;    // [2][En][ldz bytes]
+  long long ldz;
+  int En;            // roundup(dim_k, 128)
+  int n_half;
+  int side;          // the view whose rows are written; B is the other view's Zt
+  int nk;            // 128-byte K-steps over N_pad (per plane)
+  float* out;        // [rows_pad][ldo]
+  long long ldo;
+};
+
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[4 * kXvStage];
+  lds_char* lds = (lds_char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int Ei = blockIdx.x, Mi = blockIdx.y, side = p.side;
+
+  // A: rows Mi * 128 .. of the coefficient planes; B: rows e of the OTHER view's Zt; K along both
+  const char* arow = p.gbuf + (long long)Mi * kXvTile * p.ldg;
+  const char* brow = p.zt + ((long long)(1 - side) * p.En + (long long)Ei * kXvTile) * p.ldz;
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // steps kk = plane * nk + k: the planes one after the other over the same B K-steps
+  const int nsteps = p.planes * p.nk;
+  xv_stage(arow, p.ldg, lds, w, lane);
+  xv_stage(brow, p.ldz, lds + kXvStage, w, lane);
+  for (int kk = 0; kk < nsteps; ++kk) {
+    // as xv_tile_gemm
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (kk + 1 < nsteps) {
+      lds_char* nxt = lds + ((kk + 1) & 1) * 2 * kXvStage;
+      const int pl = (kk + 1) >= p.nk ? 1 : 0, k = (kk + 1) - pl * p.nk;
+      xv_stage(arow + (long long)pl * p.plane_bytes + (long long)k * kKStepBytes, p.ldg, nxt, w, lane);
+      xv_stage(brow + (long long)k * kKStepBytes, p.ldz, nxt + kXvStage, w, lane);
+    }
+    if (kk == p.nk) {  // the residual plane is done: back to G's scale before the hi plane
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] *= 1.0f / kXvLoScale;
+    }
+    const lds_char* aimg = lds + (kk & 1) * 2 * kXvStage;
+    xv_mma_step<T>(aimg, aimg + kXvStage, wr, wc, r16, g, acc);
+  }
+
+  // rows of this view at or beyond N do not exist (the coefficients are zero there anyway)
+  float* out = p.out;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = Mi * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+      if (m < p.n_half) {
+        float* orow = out + ((long long)side * p.n_half + m) * p.ldo + (long long)Ei * kXvTile + 64 * wc + r16;
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) orow[16 * ni] = acc[mi][ni][r];
+      }
+    }
+}
+
+}  // namespace dev
+
+namespace {
+inline int xv_roundup(int x, int m) { return (x + m - 1) / m * m; }
+inline int xv_npad(const Geometry& g) { return xv_roundup(g.rows / 2, dev::kXvTile); }
+inline int xv_en(const Geometry& g) { return xv_roundup(g.dim_k, dev::kXvTile); }
+
+void xv_check(DType comp, const Geometry& g, const char* who) {
+  NTXENT_CHECK(g.world == 1, std::string(who) + ": one rank only (build the geometry with world = 1)");
+  NTXENT_CHECK(comp == DType::F32 || comp == DType::F16 || comp == DType::BF16,
+               std::string(who) + ": fp32 | fp16 | bf16 rows");
+  const size_t es = dtype_size(comp);
+  const int n = g.rows / 2, np = xv_npad(g);
+  // the tile GEMM reads rows [0, N_pad) and [N, N + N_pad) and K bytes [0, nk * 128) of every row;
+  // the partials hold rows_pad / 256 slots, which must be the N_pad / 128 tiles per side
+  NTXENT_CHECK(np <= g.rows_pad && n + np <= g.rows_pad && g.col_tiles == np / dev::kXvTile &&
+                   ((size_t)g.dim_k * es) % kKStepBytes == 0 && g.dim_k >= 1 && g.dim_k <= g.ld_k &&
+                   ((size_t)g.ld_k * es) % 16 == 0,
+               std::string(who) + ": geometry does not pad rows to 256 and K to 128 bytes");
+}
+
+dev::XvParams xv_params(DType comp, const void* zq, const Geometry& g) {
+  const size_t es = dtype_size(comp);
+  dev::XvParams p{};
+  p.zq = static_cast<const char*>(zq);
+  p.ldb = (long long)g.ld_k * (long long)es;
+  p.n_half = g.rows / 2;
+  p.rows_pad = g.rows_pad;
+  p.nk = (int)((size_t)g.dim_k * es / kKStepBytes);
+  p.nT = xv_npad(g) / dev::kXvTile;
+  p.scale2 = g.inv_temp * dev::kLog2e;
+  return p;
+}
+}  // namespace
+
+static size_t xv_part_bytes(const Geometry& g) { return (size_t)g.col_tiles * g.rows_pad * sizeof(float2); }
+size_t xview_fwd_scratch_bytes(const Geometry& g) { return xv_part_bytes(g) + (size_t)(g.rows / 2) * sizeof(double); }
+static int xv_planes(DType comp) { return comp == DType::F32 ? 1 : 2; }
+// 4 N_pad^2 bytes in every plan: 16-bit plans hold two planes, so their coefficients take as much
+// as one fp32 square would (twice a single 16-bit G). The caller keeps the peak down by releasing
+// zq before the dZ slab and coef / zt before dh, not by a smaller block.
+size_t xview_coef_bytes(DType comp, const Geometry& g) {
+  return (size_t)xv_planes(comp) * xv_npad(g) * xv_npad(g) * dtype_size(comp);
+}
+size_t xview_zt_bytes(DType comp, const Geometry& g) { return (size_t)2 * xv_en(g) * xv_npad(g) * dtype_size(comp); }
+size_t xview_dz_bytes(const Geometry& g) { return (size_t)g.rows_pad * g.dim_n * sizeof(float); }
+
+void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g, float* lse2, float* cpos,
+                      float* loss, void* scratch, hipStream_t stream) {
+  xv_check(comp, g, "xview_fwd");
+  NTXENT_CHECK(zq && ypos && lse2 && cpos && loss && scratch, "xview_fwd: null buffer");
+  dev::XvParams p = xv_params(comp, zq, g);
+  // scratch: the partials [nT][rows_pad] (every entry that is read is written), then the pairs'
+  // loss terms [N] (fp64; the partials are a multiple of 8 bytes)
+  float2* part = static_cast<float2*>(scratch);
+  double* lpair = reinterpret_cast<double*>(static_cast<char*>(scratch) + xv_part_bytes(g));
+  p.part = part;
+  p.ypos = ypos;
+  const int ntiles = p.nT * p.nT;
+  auto go = [&](auto tc) {
+    using Tc = decltype(tc);
+    hipLaunchKernelGGL((dev::xview_fwd_kernel<Tc>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+  };
+  if (comp == DType::F32) go(float{});
+  else if (comp == DType::F16) go(_Float16{});
+  else go(__bf16{});
+  const int n = g.rows / 2;
+  hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
+                     ypos, lse2, cpos, lpair, n, g.rows_pad, p.nT);
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n, loss);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_coef(DType comp, const void* zq, const float* lse2, const float* cpos, const Geometry& g, void* coef,
+                        void* zt, hipStream_t stream) {
+  xv_check(comp, g, "xview_coef");
+  NTXENT_CHECK(zq && lse2 && cpos && coef && zt, "xview_coef: null buffer");
+  const size_t es = dtype_size(comp);
+  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
+  dev::XvParams p = xv_params(comp, zq, g);
+  p.lse2 = lse2;
+  p.cpos = cpos;
+  p.gbuf = static_cast<char*>(coef);
+  p.ldg = (long long)np * (long long)es;
+  p.plane_bytes = (long long)np * p.ldg;
+  const int ntiles = p.nT * p.nT;
+  auto go = [&](auto tc) {
+    using Tc = decltype(tc);
+    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2), dim3(256), 0, stream,
+                       static_cast<const Tc*>(zq), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
+                       (long long)np);
+    hipLaunchKernelGGL((dev::xview_coef_kernel<Tc>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+  };
+  if (comp == DType::F32) go(float{});
+  else if (comp == DType::F16) go(_Float16{});
+  else go(__bf16{});
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream) {
+  xv_check(comp, g, "xview_dz");
+  NTXENT_CHECK(coef && zt && dz, "xview_dz: null buffer");
+  const size_t es = dtype_size(comp);
+  const int np = xv_npad(g), en = xv_en(g);
+  // the dZ tiles write columns [0, En) of rows [0, R) of the [rows_pad][dim_n] slab
+  NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, "xview_dz: dim_n < roundup(dim_k, 128)");
+  dev::XvDzParams q{};
+  q.gbuf = static_cast<const char*>(coef);
+  q.ldg = (long long)np * (long long)es;
+  q.plane_bytes = (long long)np * q.ldg;
+  q.planes = xv_planes(comp);
+  q.zt = static_cast<const char*>(zt);
+  q.ldz = (long long)np * (long long)es;
+  q.En = en;
+  q.n_half = g.rows / 2;
+  q.nk = (int)((size_t)np * es / kKStepBytes);
+  q.out = dz;
+  q.ldo = g.dim_n;
+  const dim3 grid(en / dev::kXvTile, np / dev::kXvTile);
+  auto go = [&](auto tc) {
+    using Tc = decltype(tc);
+    // view 1's rows from G, G -> G^T in place, view 2's rows from G^T: both products stream K-major
+    // coefficient rows by LDS-DMA
+    q.side = 0;
+    hipLaunchKernelGGL((dev::xview_dz_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, q);
+    hipLaunchKernelGGL((dev::xview_gt_kernel<Tc>), dim3(np / 64, np / 64, q.planes), dim3(256), 0, stream,
+                       static_cast<Tc*>(coef), (long long)np, (long long)np * np);
+    q.side = 1;
+    hipLaunchKernelGGL((dev::xview_dz_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, q);
+  };
+  if (comp == DType::F32) go(float{});
+  else if (comp == DType::F16) go(_Float16{});
+  else go(__bf16{});
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace ntxent

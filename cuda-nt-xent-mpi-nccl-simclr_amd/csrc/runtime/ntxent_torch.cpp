@@ -278,6 +278,98 @@ std::vector<at::Tensor> positive_rank(const at::Tensor& h, const std::string& co
   return pos_rank(st[0], *P);
 }
 
+// ---- cross-view InfoNCE (kernels/xview_kernels.hip) -----------------------------------------
+// The CLIP-form loss of stacked views h = [h1; h2] on the current stream: the row prologue, the
+// N x N tile GEMM with its LSE epilogue and the LSE merge. The compute dtype resolves as
+// choose_compute does; "fp8" computes in fp16 (these kernels have no fp8 operands).
+// Returns {loss, inv, lse2, cpos}: what xview_backward needs besides h (the unit rows are not
+// kept: the backward runs the row prologue again, and releases them before its largest buffer).
+static std::shared_ptr<Plan> xview_plan(const at::Tensor& h, double T, DType comp) {
+  return get_plan((int)h.size(0), (int)h.size(1), 1, 0, T, dtype_name(comp), h.device().index());
+}
+
+std::vector<at::Tensor> xview_forward(const at::Tensor& h, double T, const std::string& compute) {
+  check_input(h, "h");
+  NTXENT_CHECK(h.dim() == 2, "h must be 2-D [2N, d]");
+  NTXENT_CHECK(h.size(0) > 0 && h.size(0) % 2 == 0, "h must hold an even number of rows (two stacked views)");
+  const at::DeviceGuard guard(h.device());
+  const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
+  auto P = xview_plan(h, T, comp);
+  const Geometry& g = P->g;
+  const auto st = prep(h, *P, c10::nullopt, c10::nullopt);  // {zq, inv, ypos, -}
+  auto scratch = at::empty({(long)((xview_fwd_scratch_bytes(g) + 7) / 8)}, opts(h, at::kDouble));
+  auto lse2 = at::empty({g.rows_pad}, opts(h, at::kFloat));
+  auto cpos = at::empty({g.rows_pad}, opts(h, at::kFloat));
+  auto loss = at::empty({}, opts(h, at::kFloat));
+  launch_xview_fwd(comp, st[0].data_ptr(), st[2].data_ptr<float>(), g, lse2.data_ptr<float>(), cpos.data_ptr<float>(),
+                   loss.data_ptr<float>(), scratch.data_ptr(), cur_stream(h));
+  return {loss, st[1], lse2, cpos};
+}
+
+// want_tau: also dL/dtau times grad_out, a 0-d fp32 tensor; undefined otherwise. compute: the
+// forward's.
+static std::pair<at::Tensor, at::Tensor> xview_backward_impl(const at::Tensor& h, const at::Tensor& inv,
+                                                             const at::Tensor& lse2, const at::Tensor& cpos,
+                                                             const at::Tensor& grad_out, double T,
+                                                             const std::string& compute, bool want_tau) {
+  check_input(h, "h");
+  const at::DeviceGuard guard(h.device());
+  const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
+  auto P = xview_plan(h, T, comp);
+  const Geometry& g = P->g;
+  NTXENT_CHECK(inv.numel() == g.rows && lse2.numel() == g.rows_pad && cpos.numel() == g.rows_pad &&
+                   inv.scalar_type() == at::kFloat && lse2.scalar_type() == at::kFloat &&
+                   cpos.scalar_type() == at::kFloat,
+               "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
+  const hipStream_t stream = cur_stream(h);
+  auto go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
+  // buffers live only as long as a stage needs them (stream-ordered reuse by the allocator): the
+  // unit rows until the coefficients exist, coefficients and transposes until the slab exists
+  auto coef = at::empty({(long)xview_coef_bytes(comp, g)}, opts(h, at::kByte));
+  auto zt = at::empty({(long)xview_zt_bytes(comp, g)}, opts(h, at::kByte));
+  {
+    // The row prologue runs a second time (a seventh launch and a second read of h) so that zq need
+    // not be saved across the step. REQUIREMENT on launch_prep: for the same h, plan and device it
+    // must reproduce the forward's zq bit for bit (no atomics, no launch-dependent summation order),
+    // because the saved lse2 / cpos were formed from the forward's zq and the coefficients
+    // exp2(cos - lse2) are formed from this one; a prologue that is not repeatable would make G
+    // inconsistent with its own normaliser. test_gpu_infonce.py::test_prep_is_bitwise_repeatable
+    // holds it to that.
+    const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
+    launch_xview_coef(comp, st[0].data_ptr(), lse2.data_ptr<float>(), cpos.data_ptr<float>(), g, coef.data_ptr(),
+                      zt.data_ptr(), stream);
+  }
+  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
+  launch_xview_dz(comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
+  coef.reset();
+  zt.reset();
+  auto dh = at::empty_like(h);
+  auto dot = at::empty({g.rows}, opts(h, at::kFloat));
+  // grad_out / (R tau) scaling, the normalisation backward and dot_i = z_i . (C z)_i
+  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
+                  go.data_ptr<float>(), dh.data_ptr(), g, stream, nullptr, 0, dot.data_ptr<float>());
+  at::Tensor dtau;
+  if (want_tau) {
+    dtau = at::empty({}, opts(h, at::kFloat));
+    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau.data_ptr<float>(), g, stream);
+  }
+  return {dh, dtau};
+}
+
+at::Tensor xview_backward(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& lse2, const at::Tensor& cpos,
+                          const at::Tensor& grad_out, double T, const std::string& compute) {
+  return xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, false).first;
+}
+
+// xview_backward plus the temperature gradient: (dh, dtau); dh is bitwise xview_backward's.
+std::tuple<at::Tensor, at::Tensor> xview_backward_tau(const at::Tensor& h, const at::Tensor& inv,
+                                                      const at::Tensor& lse2, const at::Tensor& cpos,
+                                                      const at::Tensor& grad_out, double T,
+                                                      const std::string& compute) {
+  auto r = xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, true);
+  return {r.first, r.second};
+}
+
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {
   check_input(zq, "zq");
   const at::DeviceGuard guard(zq.device());
@@ -1290,6 +1382,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keep_cos") = true);
   m.def("fused_backward", &fused_backward);
   m.def("fused_backward_tau", &fused_backward_tau);
+  m.def("xview_forward", &xview_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto");
+  m.def("xview_backward", &xview_backward);
+  m.def("xview_backward_tau", &xview_backward_tau);
   m.def("tile_list_uploads", []() { return g_tile_uploads.load(); });
   m.def("set_small_path", &ntxent::set_small_path, py::arg("on"));
   m.def("small_path_enabled", &ntxent::small_path_enabled);

@@ -3,6 +3,7 @@
   python -m ntxent_amd.models.train --steps 50 --batch 256
   python -m ntxent_amd.models.train --steps 50 --batch 256 --learnable-temperature true   # one GPU
   python -m ntxent_amd.models.train --steps 50 --batch 256 --metrics-every 10   # top-1 / top-5 every 10 steps
+  python -m ntxent_amd.models.train --steps 50 --batch 256 --loss infonce   # cross-view (CLIP-form) loss, one GPU
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
       -m ntxent_amd.models.train --steps 200 --batch 512 --ckpt-dir ckpt/ --ckpt-every 50
 """
@@ -19,11 +20,14 @@ import torch.distributed as dist
 from .trainer import SimCLRTrainer, TrainConfig
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
+    """One option per TrainConfig field (``--learnable-temperature`` for ``learnable_temperature``)."""
     ap = argparse.ArgumentParser()
     for f in dataclasses.fields(TrainConfig):
         name = "--" + f.name.replace("_", "-")
-        if f.type in ("bool", bool):
+        if f.name == "loss":
+            ap.add_argument(name, choices=("ntxent", "infonce"), default=f.default)
+        elif f.type in ("bool", bool):
             ap.add_argument(name, type=lambda s: s.lower() in ("1", "true", "yes"), default=f.default)
         elif f.type in ("int", int):
             ap.add_argument(name, type=int, default=f.default)
@@ -33,8 +37,16 @@ def main(argv=None):
             ap.add_argument(name, default=f.default)
     ap.add_argument("--pg-timeout", type=float, default=600.0,
                     help="process-group timeout (s): a rank stuck in a collective fails the job instead of hanging")
-    args = ap.parse_args(argv)
-    cfg = TrainConfig(**{f.name: getattr(args, f.name) for f in dataclasses.fields(TrainConfig)})
+    return ap
+
+
+def config_from_args(args: argparse.Namespace) -> TrainConfig:
+    return TrainConfig(**{f.name: getattr(args, f.name) for f in dataclasses.fields(TrainConfig)})
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    cfg = config_from_args(args)
     pg_timeout = timedelta(seconds=args.pg_timeout)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 and not dist.is_initialized():

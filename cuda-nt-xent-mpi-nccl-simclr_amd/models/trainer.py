@@ -26,6 +26,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
+from ..ops.infonce import InfoNCELoss
 from ..ops.ntxent import NTXentLoss
 from ..utils.checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
 from ..utils.memory import GPUMemoryTracker
@@ -73,6 +74,9 @@ class TrainConfig:
     # NTXentLoss.metrics). One extra launch sequence after the step, outside step_ms. With several
     # ranks each rank ranks its own 2 x batch rows only (negatives = 2 x batch - 2).
     metrics_every: int = 0
+    # ntxent: SimCLR's loss, every other row a negative. infonce: the cross-view (CLIP-form) loss,
+    # negatives from the other view only (InfoNCELoss); one GPU only.
+    loss: str = "ntxent"
 
 
 def _dist():
@@ -128,6 +132,11 @@ class SimCLRTrainer:
         if cfg.learnable_temperature and self.world > 1:
             raise NotImplementedError("learnable_temperature is supported on one GPU only (world == 1): the "
                                       "distributed loss does not reduce the temperature gradient across ranks")
+        if cfg.loss not in ("ntxent", "infonce"):
+            raise ValueError("loss must be ntxent or infonce")
+        if cfg.loss == "infonce" and self.world > 1:
+            raise NotImplementedError("loss='infonce' is supported on one GPU only (world == 1): the cross-view "
+                                      "loss has no distributed form")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
@@ -149,8 +158,13 @@ class SimCLRTrainer:
             self.model = torch.nn.parallel.DistributedDataParallel(
                 model, device_ids=[device.index] if device.type == "cuda" else None, bucket_cap_mb=64)
         self.opt = build_optimizer(cfg, self.model, self.world)
-        self.loss_fn = NTXentLoss(cfg.temperature, compute=cfg.compute, distributed=self.world > 1,
-                                  negatives=cfg.negatives, learnable_temperature=cfg.learnable_temperature).to(device)
+        if cfg.loss == "infonce":
+            self.loss_fn = InfoNCELoss(cfg.temperature, compute=cfg.compute,
+                                       learnable_temperature=cfg.learnable_temperature).to(device)
+        else:
+            self.loss_fn = NTXentLoss(cfg.temperature, compute=cfg.compute, distributed=self.world > 1,
+                                      negatives=cfg.negatives,
+                                      learnable_temperature=cfg.learnable_temperature).to(device)
         if cfg.learnable_temperature:
             self.opt.add_param_group({"params": [self.loss_fn.log_temperature], "weight_decay": 0.0, "lars": False})
         self.base_lrs = [g["lr"] for g in self.opt.param_groups]
@@ -224,6 +238,8 @@ class SimCLRTrainer:
                 del conf["learnable_temperature"]
             if not cfg.metrics_every:
                 del conf["metrics_every"]
+            if cfg.loss == "ntxent":
+                del conf["loss"]
             save_checkpoint(Path(cfg.ckpt_dir) / f"ckpt_{self.step}.pt", model=self.model, optimizer=self.opt,
                             step=self.step, extra=extra, rank=self.rank)
         return rec

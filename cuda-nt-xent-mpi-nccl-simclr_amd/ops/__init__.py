@@ -1,5 +1,6 @@
 """NT-Xent ops: HIP autograd op, raw reference-compatible API, pure-PyTorch oracle."""
 from . import reference  # noqa: F401
+from .infonce import InfoNCEFunction, InfoNCELoss, info_nce_loss  # noqa: F401
 from .metrics import contrastive_metrics, positive_rank  # noqa: F401
 from .ntxent import (  # noqa: F401
     NTXentFunction,

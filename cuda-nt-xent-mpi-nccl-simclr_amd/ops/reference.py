@@ -100,6 +100,59 @@ def ntxent_temperature_grad_analytic(h: torch.Tensor, temperature: float,
 
 
 # ---------------------------------------------------------------------------------------
+# Cross-view InfoNCE (the CLIP form): a row's columns are the rows of the other view only.
+# ---------------------------------------------------------------------------------------
+def cross_view_logits(h: torch.Tensor, temperature) -> torch.Tensor:
+    """``z z^T / tau`` with every same-view entry (the diagonal included) masked to -inf."""
+    R = h.shape[0]
+    z, _ = normalize(h)
+    view = torch.arange(R, device=h.device) >= R // 2
+    return (z @ z.t() / temperature).masked_fill(view.unsqueeze(0) == view.unsqueeze(1), float("-inf"))
+
+
+def info_nce_loss(h: torch.Tensor, temperature=0.07) -> torch.Tensor:
+    """Autograd-capable cross-view InfoNCE on stacked views ``h = [h1; h2]``: NT-Xent with the
+    same-view columns masked, which is ``(CE(A B^T / tau) + CE(B A^T / tau)) / 2`` of the unit towers."""
+    if h.dim() != 2 or h.shape[0] % 2:
+        raise ValueError("h must be [2N, d] with stacked views")
+    S = cross_view_logits(h, temperature)
+    return torch.nn.functional.cross_entropy(S, positive_index(h.shape[0], h.device), reduction="mean")
+
+
+def _info_nce_coefficients(h: torch.Tensor, tau: float):
+    """(z, inv, C) with C = M o (P + P^T) - 2 I_pos, M the cross-view mask (P is zero off it)."""
+    R = h.shape[0]
+    z, inv = normalize(h)
+    S = cross_view_logits(h, tau)
+    P = torch.exp(S - torch.logsumexp(S, dim=1, keepdim=True))
+    C = P + P.t()
+    C[torch.arange(R, device=h.device), positive_index(R, h.device)] -= 2.0
+    return z, inv, C
+
+
+def info_nce_backward_analytic(h: torch.Tensor, temperature: float,
+                               grad_out: float | torch.Tensor = 1.0) -> torch.Tensor:
+    """Closed-form gradient of ``info_nce_loss`` (what the HIP backward implements):
+    dL/dz = C z / (R tau), dL/dh = inv (dz - z (z . dz))."""
+    R = h.shape[0]
+    z, inv, C = _info_nce_coefficients(h, float(temperature))
+    dz = (C @ z) * (torch.as_tensor(grad_out, dtype=h.dtype, device=h.device) / (R * float(temperature)))
+    dot = (z * dz).sum(1, keepdim=True)
+    return inv.unsqueeze(1) * (dz - z * dot)
+
+
+def info_nce_temperature_grad_analytic(h: torch.Tensor, temperature: float,
+                                       grad_out: float | torch.Tensor = 1.0) -> torch.Tensor:
+    """Closed-form d loss / d tau of ``info_nce_loss``, a 0-d tensor:
+    -(1 / (2 R tau^2)) sum_i dot_i with dot_i = sum_j C_ij cos_ij = z_i . (C z)_i."""
+    R = h.shape[0]
+    tau = float(temperature)
+    z, _, C = _info_nce_coefficients(h, tau)
+    dot = (z * (C @ z)).sum(1)
+    return -torch.as_tensor(grad_out, dtype=h.dtype, device=h.device) * dot.sum() / (2.0 * R * tau * tau)
+
+
+# ---------------------------------------------------------------------------------------
 # Contrastive metrics: the rank of each row's positive among its negatives.
 # ---------------------------------------------------------------------------------------
 def _negatives_mask(rows: int, device=None) -> torch.Tensor:

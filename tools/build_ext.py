@@ -31,7 +31,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 RUNTIME_SRCS = ["engine.cpp", "engine_sym.cpp", "step.cpp", "sym_step.cpp", "rccl_comm.cpp", "trace.cpp"]
 KERNEL_SRCS = [CSRC / "kernels" / "ntxent_kernels.hip", CSRC / "kernels" / "small_kernels.hip",
-               CSRC / "kernels" / "rank_kernels.hip"]
+               CSRC / "kernels" / "rank_kernels.hip", CSRC / "kernels" / "xview_kernels.hip"]
 
 
 def _host_cxx():
