@@ -228,6 +228,11 @@ struct RawRows {
   float2* fold_pre = nullptr;   // [Rpad] scratch of the folded LSE (pre-merged row states)
   int* fold_cnt = nullptr;      // [Rpad / 64] zeroed counters (self-cleaning)
   mutable bool lse_folded = false;
+  // Set instead of lse_folded when set_lse_fold(false) alone kept the fold from running (every
+  // other condition of the fold, Z^T side blocks included, holds): the
+  // caller passes it to launch_lse, which then merges each row's partials in the fold's order, so
+  // that the toggle changes where the merge runs and not a bit of lse2, cpos or the gradient.
+  mutable bool lse_fold_order = false;
 };
 void set_lse_fold(bool on);  // default: NTXENT_LSE_FOLD (unset: on)
 bool lse_fold_enabled();
@@ -288,7 +293,9 @@ struct Q8Stats {
 void launch_lse(const float2* part, const float* ypos, float* lse2_all, float* cpos,
                 float* block_loss, float* loss_sum, const Geometry& g, hipStream_t stream,
                 DType tr_dtype = DType::F16, const void* zq = nullptr, void* zqt = nullptr,
-                const Q8Stats* q8 = nullptr, const RawRows* raw = nullptr);
+                const Q8Stats* q8 = nullptr, const RawRows* raw = nullptr, bool fold_order = false);
+// fold_order (RawRows::lse_fold_order; world 1, rows == rows_pad, rows / 2 a tile multiple): the
+// merge order of the folded LSE (sim_gemm.h lse_fold_pre / lse_fold_finish) instead of the launch's own.
 
 // Kept cosine tiles `sbuf` ([n_fwd_tiles][256*256], fragment order) -> coefficient tiles
 // `cbuf` ([row_tiles][col_tiles][256*256], row-major per tile) with C = P + P^T - 2 I_pos;

@@ -540,6 +540,10 @@ struct LseArgs {
   float* lmin;
   // > 0: the loss sum as one fixed-point ticket (lse_block), 2^F units per nat (lse_loss_fx)
   double loss_fx;
+  // 1: merge in the folded LSE's order (lse_fold_pre / lse_fold_finish): lanes 0-3 of an item take
+  // a contiguous quarter of the column tiles each, in tile order, lane 0 merges the four states in
+  // lane order, and the diagonal tile's partial of row j joins last
+  int fold_order;
 };
 // Block `bid` of the nb LSE blocks (the last of them to finish sums the loss).
 __device__ __forceinline__ void lse_block(const LseArgs& a, int bid, int nb, float* red, int& last) {
@@ -560,6 +564,40 @@ __device__ __forceinline__ void lse_block(const LseArgs& a, int bid, int nb, flo
     // and a scale from it put the negatives' coefficients ~15 bits below their e4m3 range
     // (subnormal or zero: a 5e-2 gradient error, profiles/r5/fp8bwd_diag.log).
     float bi = kNegInf, bj = kNegInf;
+    if (a.fold_order) {  // (world 1, no fp8 backward: launch_lse checks)
+      const int nt = j / kTile;
+      if (q < 4) {
+        const int t1 = Tc * (q + 1) / 4;
+        for (int tb = Tc * q / 4; tb < t1; tb += 8) {  // 8 tiles per round of loads (Tc <= 32: one round)
+          float2 vi[8], vj[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int t = tb + u < t1 ? tb + u : tb;  // clamped: duplicates are skipped below
+            vi[u] = part[(long long)t * Rpad + i];
+            vj[u] = part[(long long)t * Rpad + j];
+          }
+#pragma unroll
+          for (int u = 0; u < 8; ++u)
+            if (tb + u < t1) {
+              lse_merge(mi, si, vi[u].x, vi[u].y);
+              if (tb + u != nt) lse_merge(mj, sj, vj[u].x, vj[u].y);
+            }
+        }
+      }
+      const int l0 = (threadIdx.x & 63) - q;  // the item's first lane
+      for (int ww = 1; ww < 4; ++ww) {
+        const float wmi = __shfl(mi, l0 + ww), wsi = __shfl(si, l0 + ww);
+        const float wmj = __shfl(mj, l0 + ww), wsj = __shfl(sj, l0 + ww);
+        if (q == 0) {
+          lse_merge(mi, si, wmi, wsi);
+          lse_merge(mj, sj, wmj, wsj);
+        }
+      }
+      if (q == 0) {
+        const float2 d = part[(long long)nt * Rpad + j];
+        lse_merge(mj, sj, d.x, d.y);
+      }
+    } else {
     // 4 column tiles per lane per round, all loads issued before the (branchy) merges: one
     // memory round trip per 32 column tiles instead of one per tile
     for (int t0 = q; t0 < Tc; t0 += 4 * kLseLanes) {
@@ -590,6 +628,7 @@ __device__ __forceinline__ void lse_block(const LseArgs& a, int bid, int nb, flo
         bi = fmaxf(bi, __shfl_xor(bi, off));
         bj = fmaxf(bj, __shfl_xor(bj, off));
       }
+    }
     }
     if (q == 0) {
       const float yp = a.ypos[i];
@@ -1492,10 +1531,13 @@ bool launch_fwd_stats(DType comp, const void* zq_local, const void* zq_all, cons
         const int nhalf = g.rows / 2;
         // (the launch is build_fwd_tiles' whole own block: its diagonal tiles come last, in panel
         // order, so the remainder is panels [rt - nstrip, rt))
-        if (raw && raw->lse2 && raw->zqt && raw->fold_pre && raw->fold_cnt && lse_fold_enabled() && nup <= ws.num_cus &&
-            g.world == 1 &&
-            g.rows == g.rows_pad && nhalf % kTile == 0 && nstrip * kTile == nhalf && diag_tail == g.row_tiles &&
-            ntiles == count_own_fwd_tiles(g)) {
+        const bool fold_fits = raw && raw->lse2 && raw->zqt && raw->fold_pre && raw->fold_cnt && nup <= ws.num_cus &&
+                               g.world == 1 && g.rows == g.rows_pad && nhalf % kTile == 0 && nstrip * kTile == nhalf &&
+                               diag_tail == g.row_tiles && ntiles == count_own_fwd_tiles(g);
+        // the fold left out by set_lse_fold(false) alone (the two conditions below hold as well): the
+        // LSE launch then merges in the fold's order (RawRows::lse_fold_order)
+        bool fold_order = fold_fits && !lse_fold_enabled();
+        if (fold_fits && lse_fold_enabled()) {
           {
             lf.on = 1;
             lf.n = nhalf;
@@ -1545,16 +1587,19 @@ bool launch_fwd_stats(DType comp, const void* zq_local, const void* zq_all, cons
             zs.ntiles = zs.tx * (g.dim_n / 64);  // (rows [dim, dim_n) of Z^T: zeros)
             const int nside = std::min(zs.ntiles, NTXENT_ZT_SIDE_PER_CU * ws.num_cus);
             if (nside < lf.ngroups) lf.on = 0;  // (every group needs its pre-merging side block)
+            if (nside < nstrip * 4) fold_order = false;
             launch_up(zs, nside);
             side_zt = true;
           }
         }
         if (!side_zt) {
           lf.on = 0;  // (the LSE launch still runs: it writes Z^T)
+          fold_order = false;
           launch_up(dev::NoSide{nup}, 0);
         }
         zt_done = side_zt;
         if (raw) raw->lse_folded = side_zt && lf.on;
+        if (raw) raw->lse_fold_order = fold_order;
 #if NTXENT_TIMING
         tb.dump("diag_up", nup, stream);
 #endif
@@ -1611,7 +1656,7 @@ static double lse_loss_fx(const Geometry& g, int nb) {
 
 void launch_lse(const float2* part, const float* ypos, float* lse2_all, float* cpos, float* block_loss,
                 float* loss_sum, const Geometry& g, hipStream_t stream, DType tr_dtype, const void* zq, void* zqt,
-                const Q8Stats* q8, const RawRows* raw) {
+                const Q8Stats* q8, const RawRows* raw, bool fold_order) {
   const int nb = lse_blocks(g);  // one workgroup per 32 pairs / pad rows
   dev::LseArgs a{part, ypos, lse2_all, cpos, block_loss, loss_sum, (float)(1.0 / (double)g.global_rows),
                  g.rows, g.rows_pad, g.col_tiles, g.rank * g.rows_pad};
@@ -1620,6 +1665,11 @@ void launch_lse(const float2* part, const float* ypos, float* lse2_all, float* c
     a.lmin = q8->lmin;
   }
   a.loss_fx = lse_loss_fx(g, nb);
+  if (fold_order) {
+    NTXENT_CHECK(g.world == 1 && q8 == nullptr && g.rows == g.rows_pad && (g.rows / 2) % kTile == 0,
+                 "lse (fold order): world 1, rows == rows_pad, rows / 2 a tile multiple");
+    a.fold_order = 1;
+  }
   if (raw) {  // Z^T = (h * inv)^T straight from the input rows (raw-operand forward)
     NTXENT_CHECK(zqt != nullptr && q8 == nullptr && raw->inv && (tr_dtype == DType::F16 || tr_dtype == DType::BF16) &&
                      g.rows == g.rows_pad && g.dim == g.dim_k, "lse (raw rows): 2-byte Z^T, rows % 256 == 0, dim % 64 == 0");

@@ -155,7 +155,7 @@ void step_forward(const StepPlan& p, const StepBuffers& b, hipStream_t s, StepCo
       launch_lse(b.part, b.ypos, b.lse2, b.cpos, b.block_loss, b.loss, g, s, p.bwd, zq_local, nullptr, &q8);
     } else if (!comm) {
       launch_lse(b.part, b.ypos, b.lse2, b.cpos, b.block_loss, b.loss, g, s, p.bwd, p.raw ? nullptr : zq_local,
-                 zt_fwd ? nullptr : zqt_local, nullptr, p.raw && !zt_fwd ? &rr : nullptr);
+                 zt_fwd ? nullptr : zqt_local, nullptr, p.raw && !zt_fwd ? &rr : nullptr, rr.lse_fold_order);
     } else {
       launch_lse(b.part, b.ypos, b.lse2, b.cpos, b.block_loss, b.loss, g, s);
     }

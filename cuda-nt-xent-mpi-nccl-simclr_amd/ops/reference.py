@@ -248,6 +248,234 @@ def sharded_forward_backward(shards: Sequence[torch.Tensor], temperature: float,
 
 
 # ---------------------------------------------------------------------------------------
+# Planted-pair probes: inputs on which ONE element (i, j) of the 2N x 2N square carries a large
+# share of two rows' gradients, so a test can see an error in that one element.
+# ---------------------------------------------------------------------------------------
+def stacked_to_pair_order(blocks: int, rows_per_block: int) -> torch.Tensor:
+    """Index map from the rank-stacked layout (``blocks`` shards ``[h1_r; h2_r]`` of
+    ``rows_per_block`` rows, one after the other) to ``global_pair_order``: row k of the stacked
+    rows is row ``map[k]`` of the re-stacked ``[view1; view2]``."""
+    n = rows_per_block // 2
+    k = torch.arange(blocks * rows_per_block)
+    r, l = k // rows_per_block, k % rows_per_block
+    return torch.where(l < n, r * n + l, blocks * n + r * n + (l - n))
+
+
+def boundary_probes(rows: int, tile: int, *, blocks: int = 1, cross_view: bool = False,
+                    return_labels: bool = False):
+    """Probes ``(i, j)``, j a negative of i, at the elements where a tiled kernel's index arithmetic
+    can be off by one. ``tile`` is the kernel's tile edge. ``rows`` is the row count of one block
+    ``[view1; view2]``; with ``blocks = W`` the rows are W such blocks stacked (the layout the
+    data-parallel kernels index: each rank's rows padded to whole tiles, positives rank-local), the
+    indices count through the stacked rows (``stacked_to_pair_order`` maps them), every block gets
+    the whole list and pairs across blocks are added. ``cross_view``: only pairs of rows of
+    different views (cross-view InfoNCE masks the others), in both directions.
+
+    Rules (asserted by tests/test_probes_cpu.py): every row occurs in at most one probe, no probe's
+    i is another's j, and no probe row is the positive of another probe row. A candidate that
+    breaks one is skipped and the next candidate of its category is tried.
+
+    Categories (labels, with ``return_labels`` a tuple of them per probe):
+
+    * ``self-up`` / ``self-lo``: ``(m-1, m)`` and ``(m+2, m+1)`` beside the self mask, m a multiple of
+      16 (``@16``), 64 (``@64``), the tile (``@tile``), and the first row of the last tile (``@last``).
+      Cross-view: the same elements of the N x N block, ``(m-1, p(m))`` and ``(p(m+2), m+1)``, which
+      there lie beside the positive.
+    * ``pos+1`` / ``pos-1``: ``(a, p(a)+1)`` and ``(a', p(a')-1)`` with a, a' in three different tiles.
+    * ``seam``: ``(n-1, n)`` and ``(n+2, n-2)``.
+    * ``last-row`` ``(R-1, x)``, ``last-col`` ``(x, R-2)``, ``first-row`` ``(0, y)``.
+    * ``corner-up``: the first rows of tile I with the last columns of tile J > I, and the last rows of
+      I with the first columns of J, each inside the corner's 16 x 16 fragment (the corner elements
+      themselves belong to the edge probes); ``corner-lo``: the same two corners of the mirror tile
+      (J, I). I is the first tile and J the last.
+    * ``cross-block`` (blocks > 1), for each block a and the next one b: two pairs (i in a, j in b)
+      near the first-row / last-column and last-row / first-column corners of a's first tile row
+      (``upper``), two pairs (i in b, j in a) near the mirrored corners (``mirror``), and one of the
+      last rows of a with a row of b (``boundary``).
+
+    Row R-1 is the positive of row n-1, row 0 of row n and row R-2 of row n-2, so the third rule
+    does not admit the seam pairs and the edge pairs as written together. Where the last tile is
+    padded (``rows % tile != 0``) the edge pairs are taken as written and the seam moves out by the
+    smallest step that is free (``(n-3, n+1)``, ``(n+3, n-4)``); else the seam is taken as written and
+    the edges move in (``(R-3, x)``, ``(x, R-4)``, ``(1, y)``)."""
+    if rows % 2 or rows < 64 or tile < 16 or blocks < 1:
+        raise ValueError("boundary_probes: need an even row count >= 64, tile >= 16, blocks >= 1")
+    pl = _ProbePlacer(rows, tile, blocks, cross_view)
+    for b in range(blocks):
+        o = b * rows
+        # (the one order that matters: the seam and edge pairs exclude each other, see above)
+        for category in ((_edge_probes, _seam_probes) if rows % tile else (_seam_probes, _edge_probes)):
+            category(pl, o)
+        _self_mask_probes(pl, o)
+        _positive_probes(pl, o)
+        _corner_probes(pl, o)
+    if blocks > 1 and not cross_view:
+        for a in range(blocks if blocks > 2 else 1):  # each block with the next (two blocks: one pair)
+            _cross_block_probes(pl, a * rows, (a + 1) % blocks * rows)
+    return (pl.probes, pl.labels) if return_labels else pl.probes
+
+
+class _ProbePlacer:
+    """The probe list under construction and its rules: ``put`` takes the first candidate of a
+    category whose rows are in range, are a (row, negative) pair, cross-view if asked, and neither
+    probe rows nor positives of probe rows already."""
+
+    def __init__(self, rows: int, tile: int, blocks: int, cross_view: bool):
+        self.R, self.n, self.t, self.blocks, self.cross_view = rows, rows // 2, tile, blocks, cross_view
+        # cross-view: the tiles are those of the N x N block Z1 Z2^T
+        self.lim = self.n if cross_view else rows
+        self.ntile = (self.lim + tile - 1) // tile
+        self.last = (self.ntile - 1) * tile  # first row of the last tile
+        self.taken, self.probes, self.labels = set(), [], []
+
+    def pos(self, k: int) -> int:
+        b, l = divmod(k, self.R)
+        return b * self.R + (l + self.n) % self.R
+
+    def free(self, i: int, j: int) -> bool:
+        total = self.blocks * self.R
+        if not (0 <= i < total and 0 <= j < total) or i == j or j == self.pos(i):
+            return False
+        if self.cross_view and (i // self.R != j // self.R or (i % self.R >= self.n) == (j % self.R >= self.n)):
+            return False
+        return i not in self.taken and j not in self.taken
+
+    def put(self, label, cands) -> bool:
+        for i, j in cands:
+            if self.free(i, j):
+                self.taken.update((i, j, self.pos(i), self.pos(j)))
+                self.probes.append((i, j))
+                self.labels.append(label)
+                return True
+        return False
+
+
+def _seam_probes(pl: _ProbePlacer, o: int) -> None:
+    n = pl.n
+    pl.put(("seam",), [(o + n - 1, o + n), (o + n - 3, o + n + 1)])
+    pl.put(("seam",), [(o + n + 2, o + n - 2), (o + n + 3, o + n - 4)])
+
+
+def _edge_probes(pl: _ProbePlacer, o: int) -> None:
+    """First and last valid rows and columns; the partners are view-1 rows from the middle of the
+    view, away from every edge (the first row's partner is the same row of view 2)."""
+    R, n = pl.R, pl.n
+    xs = [o + n // 2 + x for x in (7, 11, 13, 19, 23, 29)]
+    pl.put(("last-row",), [(o + r, x) for r in (R - 1, R - 3) for x in xs])
+    pl.put(("last-col",), [(x, o + c) for c in (R - 2, R - 4) for x in xs])
+    pl.put(("first-row",), [(o + r, x + n) for r in (0, 1) for x in xs])
+
+
+def _self_mask_probes(pl: _ProbePlacer, o: int) -> None:
+    """``(m-1, m)`` and ``(m+2, m+1)`` at the first free m of each kind of multiple (cross-view: the
+    same elements of the N x N block, which lie beside the positive). Both or neither are placed."""
+    t, lim, last = pl.t, pl.lim, pl.last
+    groups = [(("@last",) if last > t else ("@last", "@tile"), [last] if last > 0 else []),
+              (("@tile",), list(range(t, last, t))),
+              (("@64",), [m for m in range(64, lim - 2, 64) if m % t]),
+              (("@16",), [m for m in range(16, lim - 2, 16) if m % 64 and m % t])]
+    for tags, ms in groups:
+        if t == 64 and "@tile" in tags:
+            tags = tags + ("@64",)
+        for m in ms:
+            if pl.cross_view:
+                up, lo = (o + m - 1, pl.pos(o + m)), (pl.pos(o + m + 2), o + m + 1)
+            else:
+                up, lo = (o + m - 1, o + m), (o + m + 2, o + m + 1)
+            if m + 2 < lim and pl.free(*up) and pl.free(*lo):
+                pl.put(("self-up",) + tags, [up])
+                pl.put(("self-lo",) + tags, [lo])
+                break
+
+
+def _positive_probes(pl: _ProbePlacer, o: int) -> None:
+    """``(a, p(a)+1)`` and ``(a', p(a')-1)`` with a, a' in the first, a middle and the last tile, a few
+    rows into the tile (any free row of the tile will do: the candidates are tried in turn).
+    Cross-view: every other tile's rows come from view 2, so both directions occur."""
+    t, lim = pl.t, pl.lim
+    for k, T0 in enumerate(sorted({0, pl.ntile // 2, pl.ntile - 1})):
+        offs = [x for x in (5, 21, 9, 37, 45, 53, 11, 27) if T0 * t + x < min((T0 + 1) * t, lim)]
+        a0 = o + T0 * t + (pl.n if pl.cross_view and k % 2 else 0)
+        pl.put(("pos+1",), [(a0 + x, pl.pos(a0 + x) + 1) for x in offs])
+        pl.put(("pos-1",), [(a0 + x, pl.pos(a0 + x) - 1) for x in reversed(offs)])
+
+
+def _corner_probes(pl: _ProbePlacer, o: int) -> None:
+    """The two corners of the off-diagonal tile (first tile, last tile) and of its mirror, each the
+    first free element stepping diagonally into the tile from the corner."""
+    if pl.ntile < 2:
+        return
+    co = o + pl.n if pl.cross_view else o  # columns of the tile; its mirror swaps the roles
+    r1, c0, c1 = pl.t - 1, pl.last, pl.lim - 1
+    pl.put(("corner-up",), [(o + s, co + c1 - s) for s in range(1, 12)])
+    pl.put(("corner-up",), [(o + r1 - s, co + c0 + s) for s in range(3, 14)])
+    pl.put(("corner-lo",), [(co + c0 + 5 + s, o + r1 - 5 - s) for s in range(12)])
+    pl.put(("corner-lo",), [(co + c1 - 5 - s, o + 5 + s) for s in range(12)])
+
+
+def _cross_block_probes(pl: _ProbePlacer, oa: int, ob: int) -> None:
+    """Pairs with one row in the block at ``oa`` and one in the block at ``ob``."""
+    R, t = pl.R, pl.t
+    pl.put(("cross-block", "upper"), [(oa + 8 + s, ob + R - 9 - s) for s in range(16)])
+    pl.put(("cross-block", "upper"), [(oa + t - 9 - s, ob + 8 + s) for s in range(16)])
+    pl.put(("cross-block", "mirror"), [(ob + 24 + s, oa + t - 25 - s) for s in range(16)])
+    pl.put(("cross-block", "mirror"), [(ob + R - 25 - s, oa + 24 + s) for s in range(16)])
+    pl.put(("cross-block", "boundary"), [(oa + R - 5 - s, ob + 64 + s) for s in range(12)])
+
+
+def plant_pairs(h: torch.Tensor, probes: Sequence[Tuple[int, int]], c: float) -> torch.Tensor:
+    """A copy of ``h`` in which row j of every probe (i, j) is ``|h_j| (c u_i + sqrt(1 - c^2) r)``,
+    ``u_i = h_i / |h_i|`` and r the unit part of the old h_j orthogonal to h_i: ``cos_ij = c`` exactly,
+    the norm of row j unchanged. The probes must keep the rules of ``boundary_probes`` (no j is
+    another probe's row)."""
+    if not 0.0 < c < 1.0:
+        raise ValueError("plant_pairs: need 0 < c < 1")
+    out = h.clone()
+    for i, j in probes:
+        u = h[i] / h[i].norm()
+        r = h[j] - (h[j] @ u) * u
+        out[j] = h[j].norm() * (c * u + math.sqrt(1.0 - c * c) * r / r.norm())
+    return out
+
+
+def probe_signatures(h: torch.Tensor, temperature: float, probes: Sequence[Tuple[int, int]], *,
+                     grad: Optional[torch.Tensor] = None, cross_view: bool = False):
+    """(sig [k, 2], P [k]) in the dtype of ``h`` (use fp64): for probe (i, j), ``sig[:, 0]`` is the
+    share of row i's gradient that the single element (i, j) carries,
+
+        sig(a, b) = max| inv_a (P_ab + P_ba) / (R tau) (z_b - (z_a . z_b) z_a) | / max|grad_a|,
+
+    ``sig[:, 1]`` is sig(j, i), and ``P`` is P_ij, the softmax weight of column j in row i.
+    ``grad`` is dL/dh of the loss (computed here when not given); ``cross_view`` takes the softmax
+    of cross-view InfoNCE."""
+    R = h.shape[0]
+    tau = float(temperature)
+    if grad is None:
+        grad = (info_nce_backward_analytic if cross_view else ntxent_backward_analytic)(h, tau)
+    z, inv = normalize(h)
+    ii = torch.tensor([p[0] for p in probes], device=h.device)
+    jj = torch.tensor([p[1] for p in probes], device=h.device)
+    rows = torch.cat([ii, jj])
+    S = z[rows] @ z.t() / tau  # only the probe rows of the square
+    col = torch.arange(R, device=h.device)
+    if cross_view:
+        S = S.masked_fill((rows >= R // 2).unsqueeze(1) == (col >= R // 2).unsqueeze(0), float("-inf"))
+    else:
+        S = S.masked_fill(rows.unsqueeze(1) == col.unsqueeze(0), float("-inf"))
+    P = torch.exp(S - torch.logsumexp(S, dim=1, keepdim=True))
+    k = len(probes)
+    ar = torch.arange(k, device=h.device)
+    p_ij, p_ji = P[ar, jj], P[k + ar, ii]
+
+    def sig(a, b):
+        cos = (z[a] * z[b]).sum(1, keepdim=True)
+        part = inv[a].unsqueeze(1) * ((p_ij + p_ji) / (R * tau)).unsqueeze(1) * (z[b] - cos * z[a])
+        return part.abs().max(1).values / grad[a].abs().max(1).values
+
+    return torch.stack([sig(ii, jj), sig(jj, ii)], 1), p_ij
+
+
+# ---------------------------------------------------------------------------------------
 # What the reference computes as written (for documentation / contrast tests only).
 # ---------------------------------------------------------------------------------------
 def reference_as_written_forward(z: torch.Tensor, T: float) -> torch.Tensor:

@@ -2,8 +2,11 @@
 lse_fold_group): when the remainder is exactly the diagonal tiles of the second half of the rows
 (the headline and config 2: 16 of 32 panels), each completed 64-row group's block merges its 64
 positive pairs and adds its loss to the LSE launch's fixed-point ticket, and no LSE launch runs.
-Pinned against the unfolded path (same value up to the merge order and the per-block partial
-sums) and against the fp64 oracle; shapes where the fold does not apply must be unaffected.
+Pinned against the unfolded path and against the fp64 oracle; shapes where the fold does not
+apply must be unaffected. Where the fold applies, set_lse_fold(False) makes the LSE launch merge
+in the fold's order (RawRows::lse_fold_order), so lse2, cpos and the gradient are the same bits
+there (asserted in tests/test_gpu_probes.py) and only the loss's per-block partial sums differ;
+the tolerances below date from the launch's own merge order and still hold.
 Reference intent: /root/reference/src/ntxent_kernel.cu:202-215 (compute_loss).
 """
 import pytest
