@@ -15,6 +15,7 @@
 
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
+#include "host_common.h"
 #include "sim_gemm.h"
 
 #include <atomic>
@@ -877,25 +878,6 @@ __global__ __launch_bounds__(kTauGradThreads) void tau_grad_kernel(const float* 
 // Host side
 // ======================================================================================
 namespace {
-inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
-template <typename F>
-void dispatch_comp(DType t, F&& f) {
-  switch (t) {
-    case DType::F32: f(float{}); break;
-    case DType::F16: f(_Float16{}); break;
-    case DType::BF16: f(__bf16{}); break;
-    case DType::FP8: NTXENT_CHECK(false, "fp8 is a GEMM operand type only"); break;
-  }
-}
-
-// GEMM operand types (fp8 included).
-template <typename F>
-void dispatch_gemm(DType t, F&& f) {
-  if (t == DType::FP8) f(dev::fp8e4m3{});
-  else dispatch_comp(t, f);
-}
-
 // fp8 forward GEMMs: accumulators are products of e4m3(z * 256) values.
 // fp8 forward GEMMs: the block-scaled MFMA applies each row's E8M0 scale (stored right after
 // the row's dim_k8 bytes), so accumulators are unscaled dot products like the other dtypes.

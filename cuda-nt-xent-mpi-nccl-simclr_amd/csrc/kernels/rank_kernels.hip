@@ -11,9 +11,8 @@
 //   pos_rank_init   : a wave per positive pair: t_i = t_p(i) (fp32 dot over the stored rows, fixed
 //                     lane tree), rank = 0, hard_neg_cos = the integer image of -inf.
 //   pos_rank_kernel : one 128 x 128 tile of zq zq^T per workgroup over the upper triangle of the
-//                     tile grid (xcd_remap order). 4 waves, 64 x 64 each (4 x 4 MFMA blocks of
-//                     16 x 16), fp32 accumulators; operands staged 128 B of K per row per step by
-//                     global_load_lds into a double-buffered, XOR-swizzled LDS image. Epilogue:
+//                     tile grid (xcd_remap order), by tile128.h's MFMA loop; a diagonal tile
+//                     stages one operand image and reads it as both. Epilogue:
 //                     compare against t, count and take the maximum per row (the tile's columns
 //                     are the rows' negatives) and, off the diagonal, per column (the tile's rows
 //                     are the columns' negatives: cos is symmetric); counts and maxima are reduced
@@ -24,13 +23,13 @@
 //   pos_rank_finish : hard_neg_cos back from its integer image to fp32, in place.
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
+#include "host_common.h"
+#include "tile128.h"
 
 namespace ntxent {
 namespace dev {
 
-constexpr int kRankTile = 128;
-constexpr int kRankThreads = 256;
-constexpr int kRankStage = kRankTile * kKStepBytes;  // LDS bytes of one operand's K-step (16 KiB)
+constexpr int kRankTile = kTile128;
 
 struct RankParams {
   const char* zq;   // [rows_pad][ldb bytes] unit rows (zero K padding, zero pad rows)
@@ -94,33 +93,13 @@ __global__ __launch_bounds__(256) void pos_rank_finish_kernel(int* hard, int R) 
 }
 
 // ---- the tile kernel ---------------------------------------------------------------------
-// LDS image of a [128 rows][128 B] K-step: 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7).
-// Two rows share a 256-byte bank row, so the 16 rows x one chunk of a ds_read_b128 lane group
-// (rows 0-3 and 12-15 at chunk c, rows 4-11 at chunk c ^ 1) land on 16 different 16-byte slots.
-__device__ __forceinline__ int rk_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// Stage K-step bytes [0, 128) of 128 rows starting at `src` (rows ldb apart) into `dst`: every
-// wave moves 4 pieces of 1 KiB (8 rows); LDS is written lane-linear, the swizzle is applied on
-// the source address.
-__device__ __forceinline__ void rk_stage(const char* src, long long ldb, lds_char* dst, int w, int lane) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int piece = w * 4 + q;
-    const int row = piece * 8 + (lane >> 3);
-    const int lc = (lane & 7) ^ ((row >> 1) & 7);
-    __builtin_amdgcn_global_load_lds((const void*)(src + (long long)row * ldb + lc * 16),
-                                     (lds_void*)(dst + piece * 1024), 16, 0, 0);
-  }
-}
-
 // First tile index of tile row I in the row-major upper triangle (diagonal included).
 __device__ __forceinline__ int tri_start(int I, int nT) { return I * nT - (I * (I - 1)) / 2; }
 
 template <typename T>
-__global__ __launch_bounds__(kRankThreads) void pos_rank_kernel(const RankParams p) {
-  typedef typename Mfma<T>::frag frag;
+__global__ __launch_bounds__(kTile128Threads) void pos_rank_kernel(const RankParams p) {
   // ONE __shared__ object (staging ring, reused by the epilogue): see small_bwd_kernel
-  __shared__ __attribute__((aligned(16))) char smem[4 * kRankStage];
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
@@ -134,49 +113,13 @@ __global__ __launch_bounds__(kRankThreads) void pos_rank_kernel(const RankParams
   const int J = I + (b - tri_start(I, p.nT));
   const bool diag = I == J;
 
+  // A = rows of tile I, B = rows of tile J; a diagonal tile stages one image and uses it as both
   const char* arow = p.zq + (long long)I * kRankTile * p.ldb;
   const char* brow = p.zq + (long long)J * kRankTile * p.ldb;
-
   f32x4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // buffer s: A image at s * 2 * kRankStage, B image behind it (a diagonal tile stages one image
-  // and uses it as both operands)
-  rk_stage(arow, p.ldb, lds, w, lane);
-  if (!diag) rk_stage(brow, p.ldb, lds + kRankStage, w, lane);
-  for (int k = 0; k < p.nk; ++k) {
-    // step k landed for this wave; the raw barrier (no further vmcnt drain) makes it visible to
-    // every wave and orders every wave's reads of step k - 1 (lgkmcnt) before its slot is restaged
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (k + 1 < p.nk) {
-      lds_char* nxt = lds + ((k + 1) & 1) * 2 * kRankStage;
-      rk_stage(arow + (long long)(k + 1) * kKStepBytes, p.ldb, nxt, w, lane);
-      if (!diag) rk_stage(brow + (long long)(k + 1) * kKStepBytes, p.ldb, nxt + kRankStage, w, lane);
-    }
-    const lds_char* aimg = lds + (k & 1) * 2 * kRankStage;
-    const lds_char* bimg = diag ? aimg : aimg + kRankStage;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      frag a[4], bf[4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-        a[mi] = *(__attribute__((address_space(3))) const frag*)(aimg + rk_off(64 * wr + 16 * mi + r16, 4 * ks + g));
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        bf[ni] = *(__attribute__((address_space(3))) const frag*)(bimg + rk_off(64 * wc + 16 * ni + r16, 4 * ks + g));
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Mfma<T>::mma(a[mi], bf[ni], acc[mi][ni]);
-    }
-  }
-  __syncthreads();  // every wave is done with the staging images: the epilogue reuses them
+  tile128_gemm<T>(
+      lds, p.nk, [&](int k) { return Tile128Src{arow + (long long)k * kKStepBytes, p.ldb}; },
+      [&](int k) { return Tile128Src{brow + (long long)k * kKStepBytes, p.ldb}; }, diag, Tile128Plain{}, acc);
 
   // epilogue LDS: t of the tile's rows and columns | per-wave-column row (count, max) | per-wave-row
   // column (count, max)
@@ -269,33 +212,26 @@ __global__ __launch_bounds__(kRankThreads) void pos_rank_kernel(const RankParams
 
 void launch_pos_rank(DType comp, const void* zq, const Geometry& g, int* rank, float* pos_cos, float* hard_neg_cos,
                      hipStream_t stream) {
-  NTXENT_CHECK(g.world == 1, "pos_rank: one rank only (build the geometry with world = 1)");
-  NTXENT_CHECK(comp == DType::F32 || comp == DType::F16 || comp == DType::BF16, "pos_rank: fp32 | fp16 | bf16 rows");
-  const size_t es = dtype_size(comp);
+  const UnitRows u = unit_rows(comp, zq, g, "pos_rank");
   dev::RankParams p{};
-  p.zq = static_cast<const char*>(zq);
-  p.ldb = (long long)g.ld_k * (long long)es;
+  p.zq = u.ptr;
+  p.ldb = u.ldb;
   p.R = g.rows;
   p.n_half = g.rows / 2;
-  p.nk = (int)((size_t)g.dim_k * es / kKStepBytes);
+  p.nk = u.nk;
   p.nT = (g.rows + dev::kRankTile - 1) / dev::kRankTile;
   p.rank = rank;
   p.pos = pos_cos;
   p.hard = reinterpret_cast<int*>(hard_neg_cos);
-  // the tile kernel reads rows [0, nT * 128) and K bytes [0, nk * 128) of every row
-  NTXENT_CHECK(p.nT * dev::kRankTile <= g.rows_pad && (size_t)p.nk * kKStepBytes == (size_t)g.dim_k * es &&
-                   g.dim_k <= g.ld_k && p.nk >= 1,
-               "pos_rank: geometry does not pad rows to 128 and K to 128 bytes");
-  const int chunks = (int)((size_t)g.dim_k * es / 16);
+  // the tile kernel reads rows [0, nT * 128) of zq
+  NTXENT_CHECK(p.nT * dev::kRankTile <= g.rows_pad, "pos_rank: geometry does not pad rows to 128");
+  const int chunks = u.nk * (kKStepBytes / 16);
   const int ntiles = p.nT * (p.nT + 1) / 2;
-  auto go = [&](auto tc) {
+  dispatch_comp(comp, [&](auto tc) {
     using Tc = decltype(tc);
     hipLaunchKernelGGL((dev::pos_rank_init_kernel<Tc>), dim3((p.n_half + 3) / 4), dim3(256), 0, stream, p, chunks);
-    hipLaunchKernelGGL((dev::pos_rank_kernel<Tc>), dim3(ntiles), dim3(dev::kRankThreads), 0, stream, p);
-  };
-  if (comp == DType::F32) go(float{});
-  else if (comp == DType::F16) go(_Float16{});
-  else go(__bf16{});
+    hipLaunchKernelGGL((dev::pos_rank_kernel<Tc>), dim3(ntiles), dim3(dev::kTile128Threads), 0, stream, p);
+  });
   hipLaunchKernelGGL(dev::pos_rank_finish_kernel, dim3((g.rows + 255) / 256), dim3(256), 0, stream, p.hard, g.rows);
   NTXENT_HIP_CHECK(hipGetLastError());
 }

@@ -9,8 +9,7 @@
 // and (C z)[0:N] = G Z2, (C z)[N:] = G^T Z1.
 //
 //   xview_fwd_kernel  : one 128 x 128 tile of S12 per workgroup, all nT x nT tiles (no symmetry
-//                       in this block). The MFMA loop is rank_kernels.hip's (4 waves of 64 x 64,
-//                       LDS-DMA double buffer, XOR-swizzled image). Epilogue: negatives-only
+//                       in this block), by tile128.h's MFMA loop. Epilogue: negatives-only
 //                       (max, sum exp2) per row for the view-1 rows and per column for the view-2
 //                       rows, reduced in the wave and across the two waves in a fixed order, and
 //                       stored in launch_lse's `part` layout: slot J for the rows, slot I for the
@@ -35,20 +34,22 @@
 //                       N of zq, which is usually not tile aligned).
 //   xview_dz_kernel   : out = G Z2, and after xview_gt_kernel has transposed the planes in place,
 //                       G^T Z1: one 128 x 128 output tile per workgroup, K = N_pad, both operands
-//                       streamed K-major by LDS-DMA in the same MFMA loop; 16-bit plans run the
-//                       residual plane, scale the accumulators back and run the hi plane. fp32
+//                       streamed K-major by LDS-DMA in the same MFMA loop (tile128.h's, over the
+//                       K-steps of every plane); 16-bit plans run the residual plane, scale the
+//                       accumulators back and run the hi plane. fp32
 //                       output slab. Each output element is one workgroup's fixed-order sum:
 //                       deterministic.
 // launch_norm_bwd (with dot_out) and launch_tau_grad finish the backward as they are.
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
+#include "host_common.h"
+#include "tile128.h"
 
 namespace ntxent {
 namespace dev {
 
-constexpr int kXvTile = 128;
-constexpr int kXvThreads = 256;
-constexpr int kXvStage = kXvTile * kKStepBytes;  // LDS bytes of one operand's K-step (16 KiB)
+constexpr int kXvTile = kTile128;
+constexpr int kXvThreads = kTile128Threads;
 
 struct XvParams {
   const char* zq;   // [rows_pad][ldb bytes] unit rows (zero K padding, zero pad rows)
@@ -70,83 +71,22 @@ struct XvParams {
 // runs it first and scales its accumulators back (a power of two: exact) before the hi plane.
 constexpr float kXvLoScale = 2048.f;
 
-// LDS image of a [128 rows][128 B] K-step: 16-byte chunk c of row r at chunk c ^ ((r >> 1) & 7)
-// (rank_kernels.hip: conflict-free ds_read_b128 of 16 rows x one chunk).
-__device__ __forceinline__ int xv_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-// Stage K-step bytes [0, 128) of 128 rows starting at `src` (rows ld apart) into `dst`: every wave
-// moves 4 pieces of 1 KiB (8 rows); LDS is written lane-linear, the swizzle is applied on the source
-// address.
-__device__ __forceinline__ void xv_stage(const char* src, long long ld, lds_char* dst, int w, int lane) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int piece = w * 4 + q;
-    const int row = piece * 8 + (lane >> 3);
-    const int lc = (lane & 7) ^ ((row >> 1) & 7);
-    __builtin_amdgcn_global_load_lds((const void*)(src + (long long)row * ld + lc * 16),
-                                     (lds_void*)(dst + piece * 1024), 16, 0, 0);
-  }
-}
-
-// One K-step of the 128 x 128 tile from the staged images: 4 x 4 MFMA blocks of 16 x 16 per wave.
-template <typename T>
-__device__ __forceinline__ void xv_mma_step(const lds_char* aimg, const lds_char* bimg, int wr, int wc, int r16, int g,
-                                            f32x4 (&acc)[4][4]) {
-  typedef typename Mfma<T>::frag frag;
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    frag a[4], bf[4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-      a[mi] = *(__attribute__((address_space(3))) const frag*)(aimg + xv_off(64 * wr + 16 * mi + r16, 4 * ks + g));
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni)
-      bf[ni] = *(__attribute__((address_space(3))) const frag*)(bimg + xv_off(64 * wc + 16 * ni + r16, 4 * ks + g));
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Mfma<T>::mma(a[mi], bf[ni], acc[mi][ni]);
-  }
-}
-
 // acc = tile (I, J) of Z1 Z2^T: rows I * 128 .. of zq against rows N + J * 128 .. of zq. Ends with a
 // block barrier: the caller's epilogue may reuse the staging images.
 template <typename T>
-__device__ __forceinline__ void xv_tile_gemm(const XvParams& p, int I, int J, lds_char* lds, int w, int lane,
-                                             f32x4 (&acc)[4][4]) {
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+__device__ __forceinline__ void xv_tile_gemm(const XvParams& p, int I, int J, lds_char* lds, f32x4 (&acc)[4][4]) {
   const char* arow = p.zq + (long long)I * kXvTile * p.ldb;
   const char* brow = p.zq + ((long long)p.n_half + (long long)J * kXvTile) * p.ldb;
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // buffer s: A image at s * 2 * kXvStage, B image behind it
-  xv_stage(arow, p.ldb, lds, w, lane);
-  xv_stage(brow, p.ldb, lds + kXvStage, w, lane);
-  for (int k = 0; k < p.nk; ++k) {
-    // step k landed for this wave; the barrier makes it visible to every wave and orders every
-    // wave's reads of step k - 1 (lgkmcnt) before its slot is restaged
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (k + 1 < p.nk) {
-      lds_char* nxt = lds + ((k + 1) & 1) * 2 * kXvStage;
-      xv_stage(arow + (long long)(k + 1) * kKStepBytes, p.ldb, nxt, w, lane);
-      xv_stage(brow + (long long)(k + 1) * kKStepBytes, p.ldb, nxt + kXvStage, w, lane);
-    }
-    const lds_char* aimg = lds + (k & 1) * 2 * kXvStage;
-    xv_mma_step<T>(aimg, aimg + kXvStage, wr, wc, r16, g, acc);
-  }
-  __syncthreads();
+  tile128_gemm<T>(
+      lds, p.nk, [&](int k) { return Tile128Src{arow + (long long)k * kKStepBytes, p.ldb}; },
+      [&](int k) { return Tile128Src{brow + (long long)k * kKStepBytes, p.ldb}; }, false, Tile128Plain{}, acc);
 }
 
 // ---- forward: LSE partials of the tile's rows (view 1) and columns (view 2) -----------------
 template <typename T>
 __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p) {
   // ONE __shared__ object (staging ring, reused by the epilogue)
-  __shared__ __attribute__((aligned(16))) char smem[4 * kXvStage];
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
@@ -155,7 +95,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   const int N = p.n_half;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, I, J, lds, w, lane, acc);
+  xv_tile_gemm<T>(p, I, J, lds, acc);
 
   // epilogue LDS: per-wave-column row (max, sum) | per-wave-row column (max, sum)
   float* s_rm = reinterpret_cast<float*>(smem);  // [2][128]
@@ -313,7 +253,7 @@ __global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double*
 // ---- backward: the tile of G = P12 + P21^T - 2 I, stored once ---------------------------------
 template <typename T>
 __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * kXvStage];
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
@@ -322,7 +262,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p
   const int N = p.n_half;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, I, J, lds, w, lane, acc);
+  xv_tile_gemm<T>(p, I, J, lds, acc);
 
   // the tile's planes in the compute dtype, row-major [128][128] each, over the staging images
   // (64 KiB): fp32 plans one plane, G; 16-bit plans the residual plane (G - hi) * 2^11, then hi =
@@ -368,7 +308,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p
   constexpr int kCpp = kCpr * kXvTile;  // chunks per plane
   char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
 #pragma unroll
-  for (int q = 0; q < 4 * kXvStage / 16 / kXvThreads; ++q) {
+  for (int q = 0; q < kTile128Lds / 16 / kXvThreads; ++q) {
     const int idx = q * kXvThreads + tid;
     const int plane = idx / kCpp, in = idx - plane * kCpp;
     const int row = in / kCpr, cc = in - row * kCpr;
@@ -443,7 +383,7 @@ struct XvDzParams {
 
 template <typename T>
 __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[4 * kXvStage];
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
@@ -453,37 +393,26 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
   const char* arow = p.gbuf + (long long)Mi * kXvTile * p.ldg;
   const char* brow = p.zt + ((long long)(1 - side) * p.En + (long long)Ei * kXvTile) * p.ldz;
 
+  // steps kk = plane * nk + k: the planes one after the other over the same B K-steps. No end
+  // barrier: the epilogue does not touch LDS.
+  const int nk = p.nk;
   f32x4 acc[4][4];
+  tile128_gemm<T, /*kEndBarrier=*/false>(
+      lds, p.planes * nk,
+      [&](int kk) {
+        const int pl = kk >= nk ? 1 : 0, k = kk - pl * nk;
+        return Tile128Src{arow + (long long)pl * p.plane_bytes + (long long)k * kKStepBytes, p.ldg};
+      },
+      [&](int kk) { return Tile128Src{brow + (long long)(kk >= nk ? kk - nk : kk) * kKStepBytes, p.ldz}; }, false,
+      [&](int kk, f32x4(&c)[4][4]) {
+        if (kk == nk) {  // the residual plane is done: back to G's scale before the hi plane
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
+          for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // steps kk = plane * nk + k: the planes one after the other over the same B K-steps
-  const int nsteps = p.planes * p.nk;
-  xv_stage(arow, p.ldg, lds, w, lane);
-  xv_stage(brow, p.ldz, lds + kXvStage, w, lane);
-  for (int kk = 0; kk < nsteps; ++kk) {
-    // as xv_tile_gemm
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kk + 1 < nsteps) {
-      lds_char* nxt = lds + ((kk + 1) & 1) * 2 * kXvStage;
-      const int pl = (kk + 1) >= p.nk ? 1 : 0, k = (kk + 1) - pl * p.nk;
-      xv_stage(arow + (long long)pl * p.plane_bytes + (long long)k * kKStepBytes, p.ldg, nxt, w, lane);
-      xv_stage(brow + (long long)k * kKStepBytes, p.ldz, nxt + kXvStage, w, lane);
-    }
-    if (kk == p.nk) {  // the residual plane is done: back to G's scale before the hi plane
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] *= 1.0f / kXvLoScale;
-    }
-    const lds_char* aimg = lds + (kk & 1) * 2 * kXvStage;
-    xv_mma_step<T>(aimg, aimg + kXvStage, wr, wc, r16, g, acc);
-  }
+            for (int ni = 0; ni < 4; ++ni) c[mi][ni] *= 1.0f / kXvLoScale;
+        }
+      },
+      acc);
 
   // rows of this view at or beyond N do not exist (the coefficients are zero there anyway)
   float* out = p.out;
@@ -503,32 +432,27 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
 }  // namespace dev
 
 namespace {
-inline int xv_roundup(int x, int m) { return (x + m - 1) / m * m; }
-inline int xv_npad(const Geometry& g) { return xv_roundup(g.rows / 2, dev::kXvTile); }
-inline int xv_en(const Geometry& g) { return xv_roundup(g.dim_k, dev::kXvTile); }
+inline int xv_npad(const Geometry& g) { return roundup(g.rows / 2, dev::kXvTile); }
+inline int xv_en(const Geometry& g) { return roundup(g.dim_k, dev::kXvTile); }
 
-void xv_check(DType comp, const Geometry& g, const char* who) {
-  NTXENT_CHECK(g.world == 1, std::string(who) + ": one rank only (build the geometry with world = 1)");
-  NTXENT_CHECK(comp == DType::F32 || comp == DType::F16 || comp == DType::BF16,
-               std::string(who) + ": fp32 | fp16 | bf16 rows");
-  const size_t es = dtype_size(comp);
+// the unit rows as the tile GEMM reads them (zq may be null: the checks alone)
+UnitRows xv_check(DType comp, const void* zq, const Geometry& g, const char* who) {
+  const UnitRows u = unit_rows(comp, zq, g, who);
   const int n = g.rows / 2, np = xv_npad(g);
-  // the tile GEMM reads rows [0, N_pad) and [N, N + N_pad) and K bytes [0, nk * 128) of every row;
-  // the partials hold rows_pad / 256 slots, which must be the N_pad / 128 tiles per side
-  NTXENT_CHECK(np <= g.rows_pad && n + np <= g.rows_pad && g.col_tiles == np / dev::kXvTile &&
-                   ((size_t)g.dim_k * es) % kKStepBytes == 0 && g.dim_k >= 1 && g.dim_k <= g.ld_k &&
-                   ((size_t)g.ld_k * es) % 16 == 0,
-               std::string(who) + ": geometry does not pad rows to 256 and K to 128 bytes");
+  // the tile GEMM reads rows [0, N_pad) and [N, N + N_pad) of zq; the partials hold rows_pad / 256
+  // slots, which must be the N_pad / 128 tiles per side
+  NTXENT_CHECK(np <= g.rows_pad && n + np <= g.rows_pad && g.col_tiles == np / dev::kXvTile && u.ldb % 16 == 0,
+               std::string(who) + ": geometry does not pad rows to 256");
+  return u;
 }
 
-dev::XvParams xv_params(DType comp, const void* zq, const Geometry& g) {
-  const size_t es = dtype_size(comp);
+dev::XvParams xv_params(const UnitRows& u, const Geometry& g) {
   dev::XvParams p{};
-  p.zq = static_cast<const char*>(zq);
-  p.ldb = (long long)g.ld_k * (long long)es;
+  p.zq = u.ptr;
+  p.ldb = u.ldb;
   p.n_half = g.rows / 2;
   p.rows_pad = g.rows_pad;
-  p.nk = (int)((size_t)g.dim_k * es / kKStepBytes);
+  p.nk = u.nk;
   p.nT = xv_npad(g) / dev::kXvTile;
   p.scale2 = g.inv_temp * dev::kLog2e;
   return p;
@@ -549,9 +473,8 @@ size_t xview_dz_bytes(const Geometry& g) { return (size_t)g.rows_pad * g.dim_n *
 
 void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g, float* lse2, float* cpos,
                       float* loss, void* scratch, hipStream_t stream) {
-  xv_check(comp, g, "xview_fwd");
   NTXENT_CHECK(zq && ypos && lse2 && cpos && loss && scratch, "xview_fwd: null buffer");
-  dev::XvParams p = xv_params(comp, zq, g);
+  dev::XvParams p = xv_params(xv_check(comp, zq, g, "xview_fwd"), g);
   // scratch: the partials [nT][rows_pad] (every entry that is read is written), then the pairs'
   // loss terms [N] (fp64; the partials are a multiple of 8 bytes)
   float2* part = static_cast<float2*>(scratch);
@@ -559,13 +482,9 @@ void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g
   p.part = part;
   p.ypos = ypos;
   const int ntiles = p.nT * p.nT;
-  auto go = [&](auto tc) {
-    using Tc = decltype(tc);
-    hipLaunchKernelGGL((dev::xview_fwd_kernel<Tc>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
-  };
-  if (comp == DType::F32) go(float{});
-  else if (comp == DType::F16) go(_Float16{});
-  else go(__bf16{});
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+  });
   const int n = g.rows / 2;
   hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
                      ypos, lse2, cpos, lpair, n, g.rows_pad, p.nT);
@@ -575,32 +494,28 @@ void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g
 
 void launch_xview_coef(DType comp, const void* zq, const float* lse2, const float* cpos, const Geometry& g, void* coef,
                         void* zt, hipStream_t stream) {
-  xv_check(comp, g, "xview_coef");
   NTXENT_CHECK(zq && lse2 && cpos && coef && zt, "xview_coef: null buffer");
   const size_t es = dtype_size(comp);
   const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
-  dev::XvParams p = xv_params(comp, zq, g);
+  dev::XvParams p = xv_params(xv_check(comp, zq, g, "xview_coef"), g);
   p.lse2 = lse2;
   p.cpos = cpos;
   p.gbuf = static_cast<char*>(coef);
   p.ldg = (long long)np * (long long)es;
   p.plane_bytes = (long long)np * p.ldg;
   const int ntiles = p.nT * p.nT;
-  auto go = [&](auto tc) {
+  dispatch_comp(comp, [&](auto tc) {
     using Tc = decltype(tc);
     hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2), dim3(256), 0, stream,
                        static_cast<const Tc*>(zq), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
                        (long long)np);
     hipLaunchKernelGGL((dev::xview_coef_kernel<Tc>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
-  };
-  if (comp == DType::F32) go(float{});
-  else if (comp == DType::F16) go(_Float16{});
-  else go(__bf16{});
+  });
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream) {
-  xv_check(comp, g, "xview_dz");
+  xv_check(comp, nullptr, g, "xview_dz");
   NTXENT_CHECK(coef && zt && dz, "xview_dz: null buffer");
   const size_t es = dtype_size(comp);
   const int np = xv_npad(g), en = xv_en(g);
@@ -619,7 +534,7 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
   q.out = dz;
   q.ldo = g.dim_n;
   const dim3 grid(en / dev::kXvTile, np / dev::kXvTile);
-  auto go = [&](auto tc) {
+  dispatch_comp(comp, [&](auto tc) {
     using Tc = decltype(tc);
     // view 1's rows from G, G -> G^T in place, view 2's rows from G^T: both products stream K-major
     // coefficient rows by LDS-DMA
@@ -629,10 +544,7 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
                        static_cast<Tc*>(coef), (long long)np, (long long)np * np);
     q.side = 1;
     hipLaunchKernelGGL((dev::xview_dz_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, q);
-  };
-  if (comp == DType::F32) go(float{});
-  else if (comp == DType::F16) go(_Float16{});
-  else go(__bf16{});
+  });
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 

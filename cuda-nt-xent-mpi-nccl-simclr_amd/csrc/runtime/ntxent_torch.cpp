@@ -177,6 +177,17 @@ static void check_input(const at::Tensor& h, const char* name) {
   NTXENT_CHECK(h.is_contiguous(), std::string(name) + " must be contiguous");
 }
 
+// stacked views [2N, d]: 2-D with an even, non-zero row count
+static void check_stacked(const at::Tensor& h, const std::string& name = "h") {
+  NTXENT_CHECK(h.dim() == 2, name + " must be 2-D [2N, d]");
+  NTXENT_CHECK(h.size(0) > 0 && h.size(0) % 2 == 0, name + " must hold an even number of rows (two stacked views)");
+}
+
+// the first element of the incoming gradient as a contiguous fp32 [1] tensor on its device
+static at::Tensor grad_scalar(const at::Tensor& grad_out) {
+  return grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
+}
+
 static at::TensorOptions opts(const at::Tensor& like, at::ScalarType t) {
   return at::TensorOptions().dtype(t).device(like.device());
 }
@@ -269,8 +280,7 @@ std::vector<at::Tensor> pos_rank(const at::Tensor& zq, const Plan& P) {
 // kernel has no fp8 operands).
 std::vector<at::Tensor> positive_rank(const at::Tensor& h, const std::string& compute, bool use_mixed_precision) {
   check_input(h, "h");
-  NTXENT_CHECK(h.dim() == 2, "h must be 2-D [2N, d]");
-  NTXENT_CHECK(h.size(0) > 0 && h.size(0) % 2 == 0, "h must hold an even number of rows (two stacked views)");
+  check_stacked(h);
   const at::DeviceGuard guard(h.device());
   const DType comp = backward_dtype(choose_compute(h.scalar_type(), use_mixed_precision, compute));
   auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, 1.0, dtype_name(comp), h.device().index());
@@ -290,8 +300,7 @@ static std::shared_ptr<Plan> xview_plan(const at::Tensor& h, double T, DType com
 
 std::vector<at::Tensor> xview_forward(const at::Tensor& h, double T, const std::string& compute) {
   check_input(h, "h");
-  NTXENT_CHECK(h.dim() == 2, "h must be 2-D [2N, d]");
-  NTXENT_CHECK(h.size(0) > 0 && h.size(0) % 2 == 0, "h must hold an even number of rows (two stacked views)");
+  check_stacked(h);
   const at::DeviceGuard guard(h.device());
   const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
   auto P = xview_plan(h, T, comp);
@@ -322,7 +331,7 @@ static std::pair<at::Tensor, at::Tensor> xview_backward_impl(const at::Tensor& h
                    cpos.scalar_type() == at::kFloat,
                "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
   const hipStream_t stream = cur_stream(h);
-  auto go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
+  auto go = grad_scalar(grad_out);
   // buffers live only as long as a stage needs them (stream-ordered reuse by the allocator): the
   // unit rows until the coefficients exist, coefficients and transposes until the slab exists
   auto coef = at::empty({(long)xview_coef_bytes(comp, g)}, opts(h, at::kByte));
@@ -812,7 +821,7 @@ static StepBuffers step_buffers(const at::Tensor& h, const Plan& P, const StepPl
 //   sc: the kept cosines (keep_cos; always on fp8 plans), else undefined.
 std::vector<at::Tensor> fused_forward(const at::Tensor& h, double T, const std::string& compute, bool keep_cos) {
   check_input(h, "h");
-  NTXENT_CHECK(h.dim() == 2, "z must be 2-D [2N, d]");
+  check_stacked(h, "z");
   const at::DeviceGuard guard(h.device());
   // "auto" = the input-dtype policy (fp32 stays exact); mixed precision is requested by the
   // callers as an explicit "fp16".
@@ -880,7 +889,7 @@ static std::pair<at::Tensor, at::Tensor> fused_backward_impl(
                "fused_backward (fp8): kept cosines and the forward's Q8Stats required");
   const StepBufferBytes nb = step_buffer_bytes(sp);
   StepBuffers b = step_buffers(h, *P, sp, nb);
-  auto go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
+  auto go = grad_scalar(grad_out);
   auto dh = at::empty_like(h);
   b.inv = static_cast<float*>(inv.data_ptr());
   b.lse2 = static_cast<float*>(lse2.data_ptr());
@@ -1027,7 +1036,7 @@ std::tuple<at::Tensor, at::Tensor> backward_op(const at::Tensor& z_in, const at:
   }
   auto sc = coef_gemm(pr[0], pr[0], lse2, cpos, *P);
   auto slabs = dz(sc, zqt, *P);
-  auto go = grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
+  auto go = grad_scalar(grad_out);
   auto dh = norm_bwd(slabs, z, pr[1], go, *P);
   at::Tensor grad_logits;
   if (want_grad_logits) {

@@ -17,14 +17,13 @@ tau) scale + L2-normalisation backward (``csrc/kernels/xview_kernels.hip``).
 """
 from __future__ import annotations
 
-import math
-import os
 from typing import Optional
 
 import torch
 
 from . import _ext, reference
-from .ntxent import _use_reference, resolve_compute, temperature_value, temperature_wants_grad
+from .ntxent import (_reference_loss, _stack_views, _tau_grad, _tau_like, _TemperatureModule, _use_reference,
+                     resolve_compute, temperature_value, temperature_wants_grad)
 
 
 class InfoNCEFunction(torch.autograd.Function):
@@ -40,7 +39,7 @@ class InfoNCEFunction(torch.autograd.Function):
         loss, inv, lse2, cpos = C.xview_forward(h, float(temperature), compute)
         ctx.temperature = float(temperature)
         ctx.compute = compute
-        ctx.tau = None if tau is None else (tau.dtype, tau.device, tau.shape)
+        ctx.tau = _tau_like(tau)
         ctx.save_for_backward(h, inv, lse2, cpos)
         return loss
 
@@ -52,8 +51,7 @@ class InfoNCEFunction(torch.autograd.Function):
             dh = C.xview_backward(h, inv, lse2, cpos, grad_out.reshape(1), ctx.temperature, ctx.compute)
             return dh, None, None, None
         dh, dtau = C.xview_backward_tau(h, inv, lse2, cpos, grad_out.reshape(1), ctx.temperature, ctx.compute)
-        dtype, device, shape = ctx.tau
-        return dh, None, None, dtau.to(device=device, dtype=dtype).reshape(shape)
+        return dh, None, None, _tau_grad(dtau, ctx.tau)
 
 
 def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tensor] = None, compute: str = "auto",
@@ -71,18 +69,9 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
 
     One GPU only: there is no distributed form of this loss yet.
     """
-    if z2 is not None:
-        h = torch.cat([h, z2], 0)
-    if h.dim() != 2 or h.shape[0] % 2:
-        raise ValueError("expected stacked views [2N, d]")
+    h = _stack_views(h, z2)
     if _use_reference(h):
-        if h.is_cuda and os.environ.get("NTXENT_ALLOW_REFERENCE", "0") != "1":
-            raise RuntimeError("NTXENT_FORCE_REFERENCE requires NTXENT_ALLOW_REFERENCE=1")
-        if isinstance(temperature, torch.Tensor):  # autograd carries the temperature's gradient
-            if temperature.numel() != 1:
-                raise ValueError("temperature must be a float or a one-element tensor")
-            temperature = temperature.reshape(()).to(h.device)
-        return reference.info_nce_loss(h, temperature)
+        return _reference_loss(reference.info_nce_loss, h, temperature)
     comp = resolve_compute(h.dtype, use_mixed_precision, compute)
     if comp == "fp8":
         comp = "fp16"
@@ -90,7 +79,7 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
     return InfoNCEFunction.apply(h, temperature_value(temperature), comp, tau)
 
 
-class InfoNCELoss(torch.nn.Module):
+class InfoNCELoss(_TemperatureModule):
     """``nn.Module`` front end: ``InfoNCELoss(temperature)(z1, z2)`` or ``(h)``. One GPU only.
 
     ``learnable_temperature=True``: the module owns an fp32 parameter ``log_temperature``,
@@ -102,36 +91,13 @@ class InfoNCELoss(torch.nn.Module):
     def __init__(self, temperature: float = 0.07, compute: str = "auto", use_mixed_precision: bool = False,
                  learnable_temperature: bool = False, temperature_bounds=(0.01, 1.0)):
         super().__init__()
-        self.temperature = float(temperature)
         self.compute = compute
         self.use_mixed_precision = use_mixed_precision
-        self.learnable_temperature = bool(learnable_temperature)
-        self.temperature_bounds = (float(temperature_bounds[0]), float(temperature_bounds[1]))
-        if self.learnable_temperature:
-            if not 0.0 < self.temperature_bounds[0] <= self.temperature_bounds[1]:
-                raise ValueError("temperature_bounds must be 0 < low <= high")
-            self.log_temperature = torch.nn.Parameter(torch.tensor(math.log(self.temperature), dtype=torch.float32))
-
-    def current_temperature(self):
-        """The temperature the next call uses: a float, or the clamped ``log_temperature.exp()``."""
-        if not self.learnable_temperature:
-            return self.temperature
-        return self.log_temperature.exp().clamp(*self.temperature_bounds)
+        self._init_temperature(temperature, learnable_temperature, temperature_bounds)
 
     def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
         return info_nce_loss(z1, self.current_temperature(), z2=z2, compute=self.compute,
                              use_mixed_precision=self.use_mixed_precision)
 
-    def metrics(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None, topk=(1, 5)):
-        """Contrastive metrics of the same inputs (``ops.metrics.contrastive_metrics``); they rank the
-        positive against all ``2N - 2`` other rows, same-view rows included."""
-        from .metrics import contrastive_metrics
-
-        return contrastive_metrics(z1, z2=z2, topk=topk, compute=self.compute,
-                                   use_mixed_precision=self.use_mixed_precision)
-
     def extra_repr(self) -> str:
-        s = f"temperature={self.temperature}, compute={self.compute}"
-        if self.learnable_temperature:
-            s += f", learnable_temperature=True, temperature_bounds={self.temperature_bounds}"
-        return s
+        return f"temperature={self.temperature}, compute={self.compute}" + self._temperature_repr()

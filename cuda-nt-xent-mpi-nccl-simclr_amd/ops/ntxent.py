@@ -69,6 +69,73 @@ def refuse_temperature_grad(temperature, where: str) -> None:
             "distributed paths do not reduce its gradient across ranks. Pass a float or a detached tensor.")
 
 
+# ---- what ntxent_loss and ops.infonce.info_nce_loss share ---------------------------------
+def _stack_views(h: torch.Tensor, z2: Optional[torch.Tensor]) -> torch.Tensor:
+    """``[h; z2]`` (or ``h`` as it is), checked to be stacked views ``[2N, d]``."""
+    if z2 is not None:
+        h = torch.cat([h, z2], 0)
+    if h.dim() != 2 or h.shape[0] % 2:
+        raise ValueError("expected stacked views [2N, d]")
+    return h
+
+
+def _reference_loss(oracle, h: torch.Tensor, temperature) -> torch.Tensor:
+    """The eager ``oracle(h, temperature)`` of ``ops.reference`` for rows ``_use_reference`` sends there."""
+    if h.is_cuda and os.environ.get("NTXENT_ALLOW_REFERENCE", "0") != "1":
+        raise RuntimeError("NTXENT_FORCE_REFERENCE requires NTXENT_ALLOW_REFERENCE=1")
+    if isinstance(temperature, torch.Tensor):  # autograd carries the temperature's gradient
+        if temperature.numel() != 1:
+            raise ValueError("temperature must be a float or a one-element tensor")
+        temperature = temperature.reshape(()).to(h.device)
+    return oracle(h, temperature)
+
+
+def _tau_like(tau: Optional[torch.Tensor]):
+    """What an autograd Function keeps of the temperature tensor whose gradient is wanted."""
+    return None if tau is None else (tau.dtype, tau.device, tau.shape)
+
+
+def _tau_grad(dtau: torch.Tensor, like) -> torch.Tensor:
+    """The kernels' 0-d fp32 dL/dtau in the temperature's own dtype, device and shape (``_tau_like``)."""
+    dtype, device, shape = like
+    return dtau.to(device=device, dtype=dtype).reshape(shape)
+
+
+class _TemperatureModule(torch.nn.Module):
+    """What NTXentLoss and InfoNCELoss share: the fixed or learnable temperature and ``metrics``."""
+
+    def _init_temperature(self, temperature, learnable_temperature, temperature_bounds) -> None:
+        self.temperature = float(temperature)
+        self.learnable_temperature = bool(learnable_temperature)
+        self.temperature_bounds = (float(temperature_bounds[0]), float(temperature_bounds[1]))
+        if self.learnable_temperature:
+            if not 0.0 < self.temperature_bounds[0] <= self.temperature_bounds[1]:
+                raise ValueError("temperature_bounds must be 0 < low <= high")
+            self.log_temperature = torch.nn.Parameter(torch.tensor(math.log(self.temperature), dtype=torch.float32))
+
+    def current_temperature(self):
+        """The temperature the next call uses: a float, or the clamped ``log_temperature.exp()``."""
+        if not self.learnable_temperature:
+            return self.temperature
+        return self.log_temperature.exp().clamp(*self.temperature_bounds)
+
+    def metrics(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None, topk=(1, 5)):
+        """Contrastive metrics of the same inputs ``forward`` takes (``ops.metrics.contrastive_metrics``:
+        ``top{k}``, ``mean_rank``, ``pos_cos``, ``hard_neg_cos``, ``negatives``) with the module's
+        ``compute`` and ``use_mixed_precision``; no gradient, and independent of the temperature.
+        The positive is ranked against all ``2N - 2`` other rows, same-view rows included; in a
+        distributed module against this rank's own ``2n - 2`` only, not against the global batch."""
+        from .metrics import contrastive_metrics
+
+        return contrastive_metrics(z1, z2=z2, topk=topk, compute=self.compute,
+                                   use_mixed_precision=self.use_mixed_precision)
+
+    def _temperature_repr(self) -> str:
+        if not self.learnable_temperature:
+            return ""
+        return f", learnable_temperature=True, temperature_bounds={self.temperature_bounds}"
+
+
 class NTXentFunction(torch.autograd.Function):
     """loss = NTXent(h) for stacked views h = [h1; h2] on one GPU.
 
@@ -82,7 +149,7 @@ class NTXentFunction(torch.autograd.Function):
         h = h.contiguous()
         loss, zq, zqt, inv, lse2, sc, cpos = C.fused_forward(h, float(temperature), compute, bool(keep_logits))
         ctx.temperature = float(temperature)
-        ctx.tau = None if tau is None else (tau.dtype, tau.device, tau.shape)
+        ctx.tau = _tau_like(tau)
         ctx.sc = sc if keep_logits else None  # released by the first backward
         ctx.save_for_backward(h, zq, zqt, inv, lse2, cpos)
         ctx.mark_non_differentiable()
@@ -97,8 +164,7 @@ class NTXentFunction(torch.autograd.Function):
             dh = C.fused_backward(h, zq, zqt, inv, lse2, sc, cpos, grad_out.reshape(1), ctx.temperature)
             return dh, None, None, None, None
         dh, dtau = C.fused_backward_tau(h, zq, zqt, inv, lse2, sc, cpos, grad_out.reshape(1), ctx.temperature)
-        dtype, device, shape = ctx.tau
-        return dh, None, None, None, dtau.to(device=device, dtype=dtype).reshape(shape)
+        return dh, None, None, None, _tau_grad(dtau, ctx.tau)
 
 
 def ntxent_loss(h: torch.Tensor, temperature=0.07, *, use_mixed_precision: bool = False,
@@ -119,18 +185,9 @@ def ntxent_loss(h: torch.Tensor, temperature=0.07, *, use_mixed_precision: bool 
       keep_logits: keep the cosine tiles (compute dtype) between forward and backward
         (default; saves one similarity GEMM). False recomputes them in the backward.
     """
-    if z2 is not None:
-        h = torch.cat([h, z2], 0)
-    if h.dim() != 2 or h.shape[0] % 2:
-        raise ValueError("expected stacked views [2N, d]")
+    h = _stack_views(h, z2)
     if _use_reference(h):
-        if h.is_cuda and os.environ.get("NTXENT_ALLOW_REFERENCE", "0") != "1":
-            raise RuntimeError("NTXENT_FORCE_REFERENCE requires NTXENT_ALLOW_REFERENCE=1")
-        if isinstance(temperature, torch.Tensor):  # autograd carries the temperature's gradient
-            if temperature.numel() != 1:
-                raise ValueError("temperature must be a float or a one-element tensor")
-            temperature = temperature.reshape(()).to(h.device)
-        return reference.ntxent_loss(h, temperature)
+        return _reference_loss(reference.ntxent_loss, h, temperature)
     comp = resolve_compute(h.dtype, use_mixed_precision, compute)
     keep = bool(keep_logits) or comp == "fp8"
     if temperature_wants_grad(temperature):
@@ -138,7 +195,7 @@ def ntxent_loss(h: torch.Tensor, temperature=0.07, *, use_mixed_precision: bool 
     return NTXentFunction.apply(h, temperature_value(temperature), comp, keep, None)
 
 
-class NTXentLoss(torch.nn.Module):
+class NTXentLoss(_TemperatureModule):
     """``nn.Module`` front end: ``NTXentLoss(temperature)(z1, z2)`` or ``(h)``.
 
     With ``distributed=True`` negatives come from the whole data-parallel group over RCCL/xGMI
@@ -154,28 +211,16 @@ class NTXentLoss(torch.nn.Module):
                  learnable_temperature: bool = False, temperature_bounds=(0.01, 1.0)):
         super().__init__()
         self.negatives = negatives
-        self.temperature = float(temperature)
         self.use_mixed_precision = use_mixed_precision
         self.compute = compute
         self.keep_logits = keep_logits
         self.distributed = distributed
         self.group = group
-        self.learnable_temperature = bool(learnable_temperature)
-        self.temperature_bounds = (float(temperature_bounds[0]), float(temperature_bounds[1]))
-        if self.learnable_temperature:
-            if distributed:
-                raise NotImplementedError(
-                    "NTXentLoss: learnable_temperature is supported on one GPU only; the distributed paths do "
-                    "not reduce the temperature gradient across ranks")
-            if not 0.0 < self.temperature_bounds[0] <= self.temperature_bounds[1]:
-                raise ValueError("temperature_bounds must be 0 < low <= high")
-            self.log_temperature = torch.nn.Parameter(torch.tensor(math.log(self.temperature), dtype=torch.float32))
-
-    def current_temperature(self):
-        """The temperature the next call uses: a float, or the clamped ``log_temperature.exp()``."""
-        if not self.learnable_temperature:
-            return self.temperature
-        return self.log_temperature.exp().clamp(*self.temperature_bounds)
+        if learnable_temperature and distributed:
+            raise NotImplementedError(
+                "NTXentLoss: learnable_temperature is supported on one GPU only; the distributed paths do "
+                "not reduce the temperature gradient across ranks")
+        self._init_temperature(temperature, learnable_temperature, temperature_bounds)
 
     def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
         h = z1 if z2 is None else torch.cat([z1, z2], 0)
@@ -188,22 +233,9 @@ class NTXentLoss(torch.nn.Module):
         return ntxent_loss(h, self.current_temperature(), use_mixed_precision=self.use_mixed_precision,
                            compute=self.compute, keep_logits=self.keep_logits)
 
-    def metrics(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None, topk=(1, 5)):
-        """Contrastive metrics of the same inputs ``forward`` takes (``ops.metrics.contrastive_metrics``:
-        ``top{k}``, ``mean_rank``, ``pos_cos``, ``hard_neg_cos``, ``negatives``) with the module's
-        ``compute`` and ``use_mixed_precision``; no gradient, and independent of the temperature.
-        A distributed module ranks each row against this rank's own ``2n`` rows only
-        (``negatives = 2n - 2``), not against the global batch."""
-        from .metrics import contrastive_metrics
-
-        return contrastive_metrics(z1, z2=z2, topk=topk, compute=self.compute,
-                                   use_mixed_precision=self.use_mixed_precision)
-
     def extra_repr(self) -> str:
-        s = f"temperature={self.temperature}, compute={self.compute}, distributed={self.distributed}"
-        if self.learnable_temperature:
-            s += f", learnable_temperature=True, temperature_bounds={self.temperature_bounds}"
-        return s
+        return (f"temperature={self.temperature}, compute={self.compute}, distributed={self.distributed}"
+                + self._temperature_repr())
 
 
 # ---- reference-compatible raw op API (src/binding_new.cpp:5-20) --------------------------

@@ -28,7 +28,9 @@ TABLE = {"fp32": (2e-9, 6e-6, 4.5e-7), "fp16": (1.2e-6, 8e-3, 6.1e-4), "bf16": (
 
 SHAPES = [(37, 40), (128, 64), (200, 100), (384, 256)]
 CASES = ([(n, d, "fp32") for n, d in SHAPES] + [(n, d, c) for n, d in [(200, 100), (384, 256)] for c in ("fp16", "bf16")]
-         + [(1024, 512, "fp16")])
+         + [(1024, 512, "fp16")]
+         # two tiles per side, the second all but one row padding; d = 160 is an odd number (3) of 16-bit K-steps
+         + [(129, 160, "fp32"), (129, 160, "fp16"), (129, 160, "bf16"), (37, 160, "fp16")])
 
 
 def _inputs(rows, dim, dtype, seed=0, noise=0.3):

@@ -21,17 +21,22 @@ DT = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
 # (N, d, input dtype): rows that are no tile multiple, d that is no multiple of 64, positive pairs
 # that straddle tiles, several tiles per side, all three MFMA types
 SHAPES = [(37, 40, "fp32"), (256, 64, "fp16"), (256, 64, "bf16"), (513, 100, "fp16"), (1024, 256, "bf16"),
-          (1024, 256, "fp32")]
+          (1024, 256, "fp32"),
+          # d = 160: an odd number (3) of 16-bit K-steps, on diagonal and off-diagonal tiles and on a single tile
+          (129, 160, "fp16"), (129, 160, "bf16"), (37, 160, "fp16")]
 SEED = 0
 
 
 @functools.lru_cache(maxsize=None)
 def _views(n, d, dt, seed=SEED):
     """h1 random, h2 = s * h1 + noise with one s ~ U[0, 1.5] per row: the ranks spread from 0 to
-    about 2N. Returned in the input dtype on the CPU; shared by every test of the shape."""
+    about 2N. Pair 0 takes -s: at large d and small n the draw alone leaves every positive in front
+    (37 x 160: all ranks 0), and this pair then still ranks near last. Returned in the input dtype on
+    the CPU; shared by every test of the shape."""
     g = torch.Generator().manual_seed(seed)
     h1 = torch.randn(n, d, generator=g)
     s = 1.5 * torch.rand(n, 1, generator=g)
+    s[0] = -s[0]
     h2 = s * h1 + torch.randn(n, d, generator=g)
     return torch.cat([h1, h2], 0).to(DT[dt])
 
