@@ -481,6 +481,48 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
                        void* zt, hipStream_t stream);
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream);
 
+// ---- distributed cross-view InfoNCE: rank g.rank of g.world ranks ---------------------------------
+// The global-batch form of the loss above. Every rank holds n = R/2 pairs; the global batch in pair
+// order is [a_0; ..; a_{W-1}; b_0; ..; b_{W-1}] (N = W n pairs). zq_all [W * Rpad][ld_k] holds every
+// rank's launch_prep rows in its padded slot, lse2_all [W * Rpad] every rank's LSE. Per side v of
+// this rank the rows are its view v and the columns view 1 - v of ALL ranks (both n x N blocks are
+// computed: no column partials cross ranks), the positive of local row l being column l of the own slot.
+//
+//   launch_xview_dist_fwd : 128 x 128 tiles (side, I, J), J over the n_pad / 128 column tiles of the
+//     rank slots [q_lo, q_hi) except q_skip (-1: none): negatives-only row partials into
+//     `part` [W * nT][Rpad] (slot = q * nT + local tile, row = side * n + l), and the rows' positive
+//     logits into ypos [R] from the own slot's diagonal tiles. Every (slot, valid row) is written by
+//     exactly one tile, so any split of the slots over launches gives the same bits.
+//   launch_xview_dist_lse : merges the W * nT slots of both rows of every pair in slot order; writes
+//     lse2 into this rank's slot of lse2_all (pad rows zeroed) and cpos [Rpad], and loss[0] = this
+//     rank's share sum_i (lse_i - y_ip) / (2N), in fp64: a SUM over the ranks, rounded to fp32 once,
+//     gives the loss (fp32 shares would round W + 1 times, more than the one-GPU loss does). scratch:
+//     xview_dist_lse_scratch_bytes (8-byte aligned, no initialisation needed).
+//   launch_xview_dist_zt  : zt [2][En][W * n_pad] (xview_dist_zt_bytes): view v of slot q transposed
+//     into columns [q * n_pad, (q + 1) * n_pad), zero padded.
+//   launch_xview_dist_coef: the n_pad x W n_pad coefficient block of ONE side,
+//     G_ij = exp2(y_ij - lse2_i) + exp2(y_ij - lse2_j) - 2 [j = p(i)], into `coef`
+//     (xview_dist_coef_bytes = 4 n_pad W n_pad bytes in every plan; planes as launch_xview_coef),
+//     exact zeros outside the valid rows and columns.
+//   launch_xview_dist_dz  : rows [side * n, side * n + n) of the fp32 slab dz [Rpad][dim_n]
+//     (xview_dz_bytes) = G Z over K = planes x W x n_pad (xview_dz_kernel: the residual plane, then
+//     the hi plane, the rank slots ascending inside each).
+// Side 0 then side 1 through the same `coef`, then launch_norm_bwd (whose scale is the global
+// 1 / (2N tau)). No atomics, no host sync: deterministic and capturable.
+size_t xview_dist_part_bytes(const Geometry& g);
+size_t xview_dist_lse_scratch_bytes(const Geometry& g);
+size_t xview_dist_coef_bytes(DType comp, const Geometry& g);
+size_t xview_dist_zt_bytes(DType comp, const Geometry& g);
+void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, int q_lo, int q_hi, int q_skip,
+                           float2* part, float* ypos, hipStream_t stream);
+void launch_xview_dist_lse(const float2* part, const float* ypos, const Geometry& g, float* lse2_all, float* cpos,
+                           double* loss, void* scratch, hipStream_t stream);
+void launch_xview_dist_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream);
+void launch_xview_dist_coef(DType comp, const void* zq_all, const float* lse2_all, const float* cpos,
+                            const Geometry& g, int side, void* coef, hipStream_t stream);
+void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
+                          hipStream_t stream);
+
 // ---- device utilities (reference utils::get_optimal_block_size / check_tensor_core_support
 //      at include/ntxent_kernel.cuh:80-110) ------------------------------------------------
 struct DeviceInfo {

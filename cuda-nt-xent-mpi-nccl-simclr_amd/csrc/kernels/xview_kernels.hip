@@ -40,6 +40,21 @@
 //                       output slab. Each output element is one workgroup's fixed-order sum:
 //                       deterministic.
 // launch_norm_bwd (with dot_out) and launch_tau_grad finish the backward as they are.
+//
+// Distributed form (rank r of W, the global batch [a_0; ..; a_{W-1}; b_0; ..; b_{W-1}]): per side v
+// the rows are view v of this rank and the columns view 1 - v of every rank's slot of the gathered
+// rows, so both n x N blocks are computed here and nothing but the rows and the LSE crosses ranks.
+//   xview_dist_fwd_kernel  : tiles (side, I, J), column tile J = local tile J % nT of slot J / nT;
+//                       row partials only, one slot per column tile; the positive is the own slot's
+//                       column of the row's local index. Any split of the slots over launches (own
+//                       slot first, while the others are gathered) gives the same bits.
+//   xview_lse_kernel / xview_loss_kernel : as above over W * nT slots into this rank's slot of
+//                       lse2_all; the rank's loss share stays in fp64.
+//   xview_dist_coef_kernel : ONE side's n_pad x W n_pad block G_ij = P_ij + P_ji - 2 [j = p(i)], P_ji
+//                       from the gathered LSE; side 1 swaps the operand roles and so gives the rows of
+//                       G^T directly (no in-place transpose, no gradient collective).
+//   xview_transpose_kernel : Zt[v][e][q n_pad + c] for every slot q, made locally from the gathered rows.
+//   xview_dz_kernel   : the same kernel with K = W n_pad per plane (slots ascending inside a plane).
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
 #include "host_common.h"
@@ -232,11 +247,14 @@ __global__ __launch_bounds__(256) void xview_lse_kernel(const float2* __restrict
   }
 }
 
-// loss = (sum of lpair) / R. One block: thread t sums pairs t, t + 1024, ... in order, then a fixed
-// halving tree (fp64): deterministic, no atomics.
+// (sum of lpair) / denom. One GPU: denom = R and the loss goes to loss[0]. Distributed: denom = the
+// global row count and the rank's share stays in fp64 (share64[0], loss null): the shares are summed
+// across ranks before the one rounding to fp32. One block: thread t sums pairs t, t + 1024, ... in
+// order, then a fixed halving tree (fp64): deterministic, no atomics.
 constexpr int kXvSumThreads = 1024;
 __global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double* __restrict__ lpair, int N,
-                                                                   float* __restrict__ loss) {
+                                                                   double denom, float* __restrict__ loss,
+                                                                   double* __restrict__ share64) {
   __shared__ double red[kXvSumThreads];
   double t = 0.0;
   for (int i = threadIdx.x; i < N; i += kXvSumThreads) t += lpair[i];
@@ -247,7 +265,10 @@ __global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double*
     if ((int)threadIdx.x < n) red[threadIdx.x] += red[threadIdx.x + n];
     __syncthreads();
   }
-  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (2.0 * (double)N));
+  if (threadIdx.x == 0) {
+    if (loss) loss[0] = (float)(red[0] / denom);
+    else share64[0] = red[0] / denom;
+  }
 }
 
 // ---- backward: the tile of G = P12 + P21^T - 2 I, stored once ---------------------------------
@@ -317,13 +338,16 @@ __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p
   }
 }
 
-// ---- Zt[v][e][c] = zq[v N + c][e] --------------------------------------------------------------
+// ---- Zt[v][e][q slot_cols + c] = zq[q slot_rows + v N + c][e] (blockIdx.z = 2 q + v; one GPU: q = 0) ----
 template <typename T>
 __global__ __launch_bounds__(256) void xview_transpose_kernel(const T* __restrict__ zq, T* __restrict__ zt, int N,
-                                                              int dim_k, long long ldk, int En, long long ldz) {
+                                                              int dim_k, long long ldk, int En, long long ldz,
+                                                              long long slot_rows, long long slot_cols) {
   __shared__ T tile[64][65];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int c0 = blockIdx.x * 64, e0 = blockIdx.y * 64, v = blockIdx.z;
+  const int c0 = blockIdx.x * 64, e0 = blockIdx.y * 64, v = blockIdx.z & 1;
+  zq += (long long)(blockIdx.z >> 1) * slot_rows * ldk;
+  zt += (long long)(blockIdx.z >> 1) * slot_cols;
 #pragma unroll 4
   for (int j = 0; j < 16; ++j) {
     const int c = c0 + ty + 4 * j, e = e0 + tx;
@@ -429,6 +453,184 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
     }
 }
 
+// ---- distributed form: this rank's rows against the gathered rows of every rank -------------------
+// zq_all holds W slots of rows_pad rows ([view 1 (n); view 2 (n); zero pad]). Side v: the rows are
+// view v of slot `rank`, the columns view 1 - v of the slots; column tile J of a side's n x N block
+// is local tile J % nT of slot J / nT. With n + n_pad <= rows_pad no 128-row stage leaves its slot.
+struct XvDistParams {
+  const char* zq;     // [world * rows_pad][ldb bytes]
+  long long ldb;
+  int n;              // pairs per rank
+  int rows_pad;
+  int nk;
+  int nT;             // n_pad / 128
+  int world, rank;
+  int q_lo, nq, q_skip;  // forward: the launch's column slots, nq of them from q_lo on, q_skip left out
+  int side;           // coefficient pass: the side
+  float scale2;
+  float2* part;       // forward: [world * nT][rows_pad], row side * n + l
+  float* ypos;        // forward: [>= n] positive logits of the pairs, written (side 0's own diagonal)
+  const float* lse2;  // coefficient pass: [world * rows_pad] gathered LSE
+  const float* cpos;  //                   [rows_pad] positive coefficients of this rank's rows
+  char* gbuf;         // [planes][n_pad][ldg bytes]
+  long long ldg;
+  long long plane_bytes;
+};
+
+// acc = tile (I, Jl of slot q) of side `side`. Ends with a block barrier.
+template <typename T>
+__device__ __forceinline__ void xv_dist_gemm(const XvDistParams& p, int side, int I, int q, int Jl, lds_char* lds,
+                                             f32x4 (&acc)[4][4]) {
+  const char* arow = p.zq + ((long long)p.rank * p.rows_pad + (long long)side * p.n + (long long)I * kXvTile) * p.ldb;
+  const char* brow = p.zq + ((long long)q * p.rows_pad + (long long)(1 - side) * p.n + (long long)Jl * kXvTile) * p.ldb;
+  tile128_gemm<T>(
+      lds, p.nk, [&](int k) { return Tile128Src{arow + (long long)k * kKStepBytes, p.ldb}; },
+      [&](int k) { return Tile128Src{brow + (long long)k * kKStepBytes, p.ldb}; }, false, Tile128Plain{}, acc);
+}
+
+// Forward: negatives-only (max, sum exp2) of the tile's rows, slot q * nT + Jl. Rows only: the
+// other view's rows get theirs from the other side's tiles.
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_dist_fwd_kernel(const XvDistParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
+  lds_char* lds = (lds_char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int ncol = p.nq * p.nT, per_side = p.nT * ncol;
+  const int side = b / per_side, rem = b - side * per_side;
+  const int I = rem / ncol, jj = rem - I * ncol;
+  int q = p.q_lo + jj / p.nT;
+  const int Jl = jj % p.nT;
+  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
+  const int n = p.n;
+  const bool own = q == p.rank;
+
+  f32x4 acc[4][4];
+  xv_dist_gemm<T>(p, side, I, q, Jl, lds, acc);
+
+  float* s_rm = reinterpret_cast<float*>(smem);  // [2][128] per-wave-column row (max, sum)
+  float* s_rs = s_rm + 2 * kXvTile;
+  int cl[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+  float rmx[4][4];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int li = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+      float m = kNegInf;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        // local rows and columns at or beyond n are the other view's rows or slot padding: masked by
+        // index. The positive is the own slot's column of the same local index and nothing else.
+        const bool in = (li < n) & (cl[ni] < n);
+        const bool pos = own & (cl[ni] == li);
+        const float yv = acc[mi][ni][r] * p.scale2;
+        if (in & pos & (side == 0)) p.ypos[li] = yv;
+        const float y = (in & !pos) ? yv : kNegInf;
+        acc[mi][ni][r] = y;
+        m = fmaxf(m, y);
+      }
+      rmx[mi][r] = row16_max(m);
+    }
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rt = 64 * wr + 16 * mi + 4 * g + r;
+      const float mr = rmx[mi][r];
+      float s = 0.f;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const float y = acc[mi][ni][r];
+        s += y != kNegInf ? fast_exp2(y - mr) : 0.f;
+      }
+      s = row16_sum(s);
+      if (r16 == 0) {
+        s_rm[wc * kXvTile + rt] = mr;
+        s_rs[wc * kXvTile + rt] = s;
+      }
+    }
+  __syncthreads();
+  if (tid < kXvTile) {
+    float m = s_rm[tid], s = s_rs[tid];
+    lse_merge(m, s, s_rm[kXvTile + tid], s_rs[kXvTile + tid]);
+    const int li = I * kXvTile + tid;
+    if (li < n) p.part[((long long)q * p.nT + Jl) * p.rows_pad + side * n + li] = make_float2(m, s);
+  }
+}
+
+// Coefficient pass of one side: tile (I, J) of the n_pad x W n_pad block, stored as xview_coef_kernel
+// stores its tile (column J * 128 of the planes' rows).
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_dist_coef_kernel(const XvDistParams p) {
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
+  lds_char* lds = (lds_char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int ncol = p.world * p.nT;
+  const int I = b / ncol, J = b - I * ncol;
+  const int q = J / p.nT, Jl = J - q * p.nT;
+  const int n = p.n, side = p.side;
+  const bool own = q == p.rank;
+
+  f32x4 acc[4][4];
+  xv_dist_gemm<T>(p, side, I, q, Jl, lds, acc);
+
+  constexpr bool kSplit = sizeof(T) == 2;
+  constexpr int kPlaneElems = kXvTile * kXvTile;
+  T* s_g = reinterpret_cast<T*>(smem);
+  const float* lrow = p.lse2 + (long long)p.rank * p.rows_pad + side * n;
+  const float* lcol = p.lse2 + (long long)q * p.rows_pad + (1 - side) * n;
+  int cl[4];
+  float lc[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+    lc[ni] = cl[ni] < n ? lcol[cl[ni]] : 0.f;
+  }
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rt = 64 * wr + 16 * mi + 4 * g + r;
+      const int li = I * kXvTile + rt;
+      const float lr = li < n ? lrow[li] : 0.f;
+      const float cp = li < n ? p.cpos[side * n + li] : 0.f;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const float y = acc[mi][ni][r] * p.scale2;
+        const bool ok = (li < n) & (cl[ni] < n);
+        const float c = fast_exp2(y - lr) + fast_exp2(y - lc[ni]);
+        // selects, not products: outside the valid rows and columns the exponentials may overflow
+        const float v = ok ? ((own & (cl[ni] == li)) ? cp : c) : 0.f;
+        const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
+        const T hi = from_f32<T>(v);
+        if constexpr (kSplit) {
+          s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
+          s_g[kPlaneElems + at] = hi;
+        } else {
+          s_g[at] = hi;
+        }
+      }
+    }
+  __syncthreads();
+  constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
+  constexpr int kCpp = kCpr * kXvTile;
+  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
+#pragma unroll
+  for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
+    const int idx = c * kXvThreads + tid;
+    const int plane = idx / kCpp, in = idx - plane * kCpp;
+    const int row = in / kCpr, cc = in - row * kCpr;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
+    *reinterpret_cast<u32x4*>(gt + plane * p.plane_bytes + (long long)row * p.ldg + cc * 16) = v;
+  }
+}
+
 }  // namespace dev
 
 namespace {
@@ -488,7 +690,8 @@ void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g
   const int n = g.rows / 2;
   hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
                      ypos, lse2, cpos, lpair, n, g.rows_pad, p.nT);
-  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n, loss);
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n, 2.0 * (double)n, loss,
+                     (double*)nullptr);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -508,7 +711,7 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
     using Tc = decltype(tc);
     hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2), dim3(256), 0, stream,
                        static_cast<const Tc*>(zq), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
-                       (long long)np);
+                       (long long)np, 0LL, 0LL);
     hipLaunchKernelGGL((dev::xview_coef_kernel<Tc>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
   });
   NTXENT_HIP_CHECK(hipGetLastError());
@@ -544,6 +747,141 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
                        static_cast<Tc*>(coef), (long long)np, (long long)np * np);
     q.side = 1;
     hipLaunchKernelGGL((dev::xview_dz_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, q);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+// ---- distributed form ------------------------------------------------------------------------------
+namespace {
+// The gathered rows [world * rows_pad][ld_k] as the tile kernels read them. A row stage reads 128 rows
+// from local row side * n + I * 128 of the own slot, a column stage from (1 - side) * n + Jl * 128 of
+// slot q: at most local row n + n_pad of a slot, so with n + n_pad <= rows_pad no stage reads beyond
+// its slot, and none beyond the world * rows_pad rows of the buffer.
+dev::XvDistParams xv_dist_params(DType comp, const void* zq_all, const Geometry& g, const char* who) {
+  NTXENT_CHECK(comp == DType::F32 || comp == DType::F16 || comp == DType::BF16,
+               std::string(who) + ": fp32 | fp16 | bf16 rows");
+  NTXENT_CHECK(g.world >= 1 && g.rank >= 0 && g.rank < g.world, std::string(who) + ": bad world / rank");
+  const size_t es = dtype_size(comp), kbytes = (size_t)g.dim_k * es;
+  NTXENT_CHECK(kbytes % kKStepBytes == 0 && g.dim_k <= g.ld_k && kbytes >= kKStepBytes && ((size_t)g.ld_k * es) % 16 == 0,
+               std::string(who) + ": geometry does not pad K to 128 bytes");
+  const int n = g.rows / 2, np = xv_npad(g);
+  NTXENT_CHECK(n + np <= g.rows_pad, std::string(who) + ": a 128-row stage would leave its rank slot");
+  dev::XvDistParams p{};
+  p.zq = static_cast<const char*>(zq_all);
+  p.ldb = (long long)g.ld_k * (long long)es;
+  p.n = n;
+  p.rows_pad = g.rows_pad;
+  p.nk = (int)(kbytes / kKStepBytes);
+  p.nT = np / dev::kXvTile;
+  p.world = g.world;
+  p.rank = g.rank;
+  p.q_skip = -1;
+  p.scale2 = g.inv_temp * dev::kLog2e;
+  return p;
+}
+}  // namespace
+
+size_t xview_dist_part_bytes(const Geometry& g) {
+  return (size_t)g.world * (xv_npad(g) / dev::kXvTile) * g.rows_pad * sizeof(float2);
+}
+size_t xview_dist_lse_scratch_bytes(const Geometry& g) { return (size_t)(g.rows / 2) * sizeof(double); }
+// 4 n_pad W n_pad bytes in every plan (one fp32 plane, or two 16-bit planes): one side at a time
+size_t xview_dist_coef_bytes(DType comp, const Geometry& g) {
+  return (size_t)xv_planes(comp) * xv_npad(g) * g.world * xv_npad(g) * dtype_size(comp);
+}
+size_t xview_dist_zt_bytes(DType comp, const Geometry& g) {
+  return (size_t)2 * xv_en(g) * g.world * xv_npad(g) * dtype_size(comp);
+}
+
+void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, int q_lo, int q_hi, int q_skip,
+                           float2* part, float* ypos, hipStream_t stream) {
+  NTXENT_CHECK(zq_all && part && ypos, "xview_dist_fwd: null buffer");
+  NTXENT_CHECK(0 <= q_lo && q_lo <= q_hi && q_hi <= g.world && q_skip < q_hi && (q_skip < 0 || q_skip >= q_lo),
+               "xview_dist_fwd: bad slot range");
+  dev::XvDistParams p = xv_dist_params(comp, zq_all, g, "xview_dist_fwd");
+  p.q_lo = q_lo;
+  p.nq = q_hi - q_lo - (q_skip >= 0 ? 1 : 0);
+  p.q_skip = q_skip;
+  p.part = part;
+  p.ypos = ypos;
+  if (p.nq == 0) return;
+  const int ntiles = 2 * p.nT * p.nq * p.nT;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_dist_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_dist_lse(const float2* part, const float* ypos, const Geometry& g, float* lse2_all, float* cpos,
+                           double* loss, void* scratch, hipStream_t stream) {
+  NTXENT_CHECK(part && ypos && lse2_all && cpos && loss && scratch, "xview_dist_lse: null buffer");
+  const int n = g.rows / 2, nslots = g.world * (xv_npad(g) / dev::kXvTile);
+  double* lpair = static_cast<double*>(scratch);
+  // xview_lse_kernel over this rank's slot of lse2_all: W * nT slots per row instead of nT
+  hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
+                     ypos, lse2_all + (size_t)g.rank * g.rows_pad, cpos, lpair, n, g.rows_pad, nslots);
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n,
+                     (double)g.global_rows, (float*)nullptr, loss);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_dist_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream) {
+  NTXENT_CHECK(zq_all && zt, "xview_dist_zt: null buffer");
+  xv_dist_params(comp, zq_all, g, "xview_dist_zt");
+  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
+  dispatch_comp(comp, [&](auto tc) {
+    using Tc = decltype(tc);
+    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2 * g.world), dim3(256), 0, stream,
+                       static_cast<const Tc*>(zq_all), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
+                       (long long)g.world * np, (long long)g.rows_pad, (long long)np);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_dist_coef(DType comp, const void* zq_all, const float* lse2_all, const float* cpos,
+                            const Geometry& g, int side, void* coef, hipStream_t stream) {
+  NTXENT_CHECK(zq_all && lse2_all && cpos && coef && (side == 0 || side == 1), "xview_dist_coef: bad argument");
+  dev::XvDistParams p = xv_dist_params(comp, zq_all, g, "xview_dist_coef");
+  const int np = xv_npad(g);
+  p.side = side;
+  p.lse2 = lse2_all;
+  p.cpos = cpos;
+  p.gbuf = static_cast<char*>(coef);
+  p.ldg = (long long)g.world * np * (long long)dtype_size(comp);
+  p.plane_bytes = (long long)np * p.ldg;
+  const int ntiles = p.nT * g.world * p.nT;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_dist_coef_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
+                          hipStream_t stream) {
+  NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1), "xview_dist_dz: bad argument");
+  xv_dist_params(comp, nullptr, g, "xview_dist_dz");
+  const size_t es = dtype_size(comp);
+  const int np = xv_npad(g), en = xv_en(g);
+  // the dZ tiles write columns [0, En) of rows [side * n, side * n + n) of the [rows_pad][dim_n] slab
+  NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, "xview_dist_dz: dim_n < roundup(dim_k, 128)");
+  // xview_dz_kernel with K = world * n_pad per plane: the planes' rows and Zt's rows both hold the
+  // rank slots side by side, so a plane's K-steps run through the slots in ascending order
+  dev::XvDzParams q{};
+  q.gbuf = static_cast<const char*>(coef);
+  q.ldg = (long long)g.world * np * (long long)es;
+  q.plane_bytes = (long long)np * q.ldg;
+  q.planes = xv_planes(comp);
+  q.zt = static_cast<const char*>(zt);
+  q.ldz = q.ldg;
+  q.En = en;
+  q.n_half = g.rows / 2;
+  q.side = side;
+  q.nk = (int)((size_t)q.ldg / kKStepBytes);
+  q.out = dz;
+  q.ldo = g.dim_n;
+  const dim3 grid(en / dev::kXvTile, np / dev::kXvTile);
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_dz_kernel<decltype(tc)>), grid, dim3(dev::kXvThreads), 0, stream, q);
   });
   NTXENT_HIP_CHECK(hipGetLastError());
 }

@@ -379,6 +379,88 @@ std::tuple<at::Tensor, at::Tensor> xview_backward_tau(const at::Tensor& h, const
   return {r.first, r.second};
 }
 
+// ---- distributed cross-view InfoNCE: stage ops (parallel/infonce.py and parallel/emulate.py call
+// the same three) ----------------------------------------------------------------------------------
+// P: this rank's plan (get_plan(R, d, W, r, ...), fp32 | fp16 | bf16); zq_all [W * Rpad, ld_k]: every
+// rank's prep rows in its slot.
+static void check_xview_dist(const at::Tensor& zq_all, const Plan& P) {
+  check_input(zq_all, "zq_all");
+  NTXENT_CHECK(P.comp != DType::FP8, "xview_dist: fp32 | fp16 | bf16 plans (these kernels have no fp8 operands)");
+  NTXENT_CHECK(zq_all.numel() == (long)P.g.world * P.g.rows_pad * P.g.ld_k && zq_all.scalar_type() == to_scalar(P.comp),
+               "zq_all must be [world*rows_pad, ld_k] in the plan's compute dtype");
+}
+
+// Forward tiles of both sides against the rank slots [q_lo, q_hi) except q_skip (-1: none) into
+// part (float32 [xview_dist_part_slots, rows_pad, 2]) and ypos (float32 [>= rows / 2]). The own slot
+// (q == rank) needs only this rank's rows, so its tiles can run while the others are gathered.
+void xview_dist_fwd(const at::Tensor& zq_all, const Plan& P, at::Tensor& part, at::Tensor& ypos, int q_lo, int q_hi,
+                    int q_skip) {
+  check_xview_dist(zq_all, P);
+  check_input(part, "part");
+  check_input(ypos, "ypos");
+  NTXENT_CHECK(part.numel() * 4 == (long)xview_dist_part_bytes(P.g) && part.scalar_type() == at::kFloat,
+               "part must be float32 [world * n_pad / 128, rows_pad, 2]");
+  NTXENT_CHECK(ypos.numel() >= P.g.rows / 2 && ypos.scalar_type() == at::kFloat, "ypos must be float32 [>= rows / 2]");
+  const at::DeviceGuard guard(zq_all.device());
+  launch_xview_dist_fwd(P.comp, zq_all.data_ptr(), P.g, q_lo, q_hi, q_skip,
+                        reinterpret_cast<float2*>(part.data_ptr<float>()), ypos.data_ptr<float>(), cur_stream(zq_all));
+}
+
+// Merge: writes this rank's slot of lse2_all (float32 [world * rows_pad]) and cpos (float32
+// [rows_pad]); returns this rank's share of the loss, a 0-d float64 tensor (a SUM over the ranks,
+// rounded to float32 once, gives the loss).
+at::Tensor xview_dist_lse(const at::Tensor& part, const at::Tensor& ypos, at::Tensor& lse2_all, at::Tensor& cpos,
+                          const Plan& P) {
+  check_input(part, "part");
+  NTXENT_CHECK(part.numel() * 4 == (long)xview_dist_part_bytes(P.g) && part.scalar_type() == at::kFloat,
+               "part must be float32 [world * n_pad / 128, rows_pad, 2]");
+  NTXENT_CHECK(ypos.numel() >= P.g.rows / 2 && ypos.scalar_type() == at::kFloat, "ypos must be float32 [>= rows / 2]");
+  NTXENT_CHECK(lse2_all.numel() == (long)P.g.world * P.g.rows_pad && lse2_all.scalar_type() == at::kFloat,
+               "lse2_all must be float32 [world*rows_pad]");
+  NTXENT_CHECK(cpos.numel() == P.g.rows_pad && cpos.scalar_type() == at::kFloat, "cpos must be float32 [rows_pad]");
+  const at::DeviceGuard guard(part.device());
+  auto scratch = at::empty({(long)(xview_dist_lse_scratch_bytes(P.g) / 8)}, opts(part, at::kDouble));
+  auto loss = at::empty({}, opts(part, at::kDouble));
+  launch_xview_dist_lse(reinterpret_cast<const float2*>(part.data_ptr<float>()), ypos.data_ptr<float>(), P.g,
+                        lse2_all.data_ptr<float>(), cpos.data_ptr<float>(), loss.data_ptr<double>(), scratch.data_ptr(),
+                        cur_stream(part));
+  return loss;
+}
+
+// Rank-local backward from the gathered rows and LSE: the slots' transposes, then per side the
+// coefficient block (one buffer, 4 n_pad W n_pad bytes) and its dZ rows, then the normalisation
+// backward with the global scale grad_out / (2N tau).
+at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, const at::Tensor& inv,
+                               const at::Tensor& lse2_all, const at::Tensor& cpos, const at::Tensor& grad_out,
+                               const Plan& P) {
+  check_input(h, "h");
+  check_xview_dist(zq_all, P);
+  const Geometry& g = P.g;
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+  NTXENT_CHECK(inv.numel() == g.rows && cpos.numel() == g.rows_pad && lse2_all.numel() == (long)g.world * g.rows_pad &&
+                   inv.scalar_type() == at::kFloat && cpos.scalar_type() == at::kFloat &&
+                   lse2_all.scalar_type() == at::kFloat,
+               "xview_dist_backward: inv [rows], cpos [rows_pad], lse2_all [world*rows_pad] in float32");
+  const at::DeviceGuard guard(h.device());
+  const hipStream_t stream = cur_stream(h);
+  auto go = grad_scalar(grad_out);
+  auto zt = at::empty({(long)xview_dist_zt_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto coef = at::empty({(long)xview_dist_coef_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
+  launch_xview_dist_zt(P.comp, zq_all.data_ptr(), g, zt.data_ptr(), stream);
+  for (int side = 0; side < 2; ++side) {
+    launch_xview_dist_coef(P.comp, zq_all.data_ptr(), lse2_all.data_ptr<float>(), cpos.data_ptr<float>(), g, side,
+                           coef.data_ptr(), stream);
+    launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), stream);
+  }
+  coef.reset();
+  zt.reset();
+  auto dh = at::empty_like(h);
+  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
+                  go.data_ptr<float>(), dh.data_ptr(), g, stream);
+  return dh;
+}
+
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {
   check_input(zq, "zq");
   const at::DeviceGuard guard(zq.device());
@@ -1394,6 +1476,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xview_forward", &xview_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto");
   m.def("xview_backward", &xview_backward);
   m.def("xview_backward_tau", &xview_backward_tau);
+  m.def("xview_dist_part_slots", [](const Plan& P) { return (long)(xview_dist_part_bytes(P.g) / 8 / P.g.rows_pad); });
+  m.def("xview_dist_coef_bytes", [](const Plan& P) { return (long)xview_dist_coef_bytes(P.bwd(), P.g); });
+  m.def("xview_dist_fwd", &xview_dist_fwd, py::arg("zq_all"), py::arg("plan"), py::arg("part"), py::arg("ypos"),
+        py::arg("q_lo"), py::arg("q_hi"), py::arg("q_skip") = -1);
+  m.def("xview_dist_lse", &xview_dist_lse, py::arg("part"), py::arg("ypos"), py::arg("lse2_all"), py::arg("cpos"),
+        py::arg("plan"));
+  m.def("xview_dist_backward", &xview_dist_backward, py::arg("h"), py::arg("zq_all"), py::arg("inv"),
+        py::arg("lse2_all"), py::arg("cpos"), py::arg("grad_out"), py::arg("plan"));
   m.def("tile_list_uploads", []() { return g_tile_uploads.load(); });
   m.def("set_small_path", &ntxent::set_small_path, py::arg("on"));
   m.def("small_path_enabled", &ntxent::small_path_enabled);

@@ -67,7 +67,7 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
         fp16: these kernels have no fp8 operands (as the contrastive metrics).
       use_mixed_precision: fp32 inputs are computed in fp16 (fp32 accumulate) if True.
 
-    One GPU only: there is no distributed form of this loss yet.
+    One GPU; the global-batch form over a process group is ``parallel.dist_info_nce_loss``.
     """
     h = _stack_views(h, z2)
     if _use_reference(h):
@@ -80,7 +80,8 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
 
 
 class InfoNCELoss(_TemperatureModule):
-    """``nn.Module`` front end: ``InfoNCELoss(temperature)(z1, z2)`` or ``(h)``. One GPU only.
+    """``nn.Module`` front end: ``InfoNCELoss(temperature)(z1, z2)`` or ``(h)``. One GPU
+    (``parallel.DistInfoNCELoss`` for the data-parallel batch).
 
     ``learnable_temperature=True``: the module owns an fp32 parameter ``log_temperature``,
     initialised to ``log(temperature)``, and evaluates the loss at

@@ -291,7 +291,13 @@ def boundary_probes(rows: int, tile: int, *, blocks: int = 1, cross_view: bool =
     * ``cross-block`` (blocks > 1), for each block a and the next one b: two pairs (i in a, j in b)
       near the first-row / last-column and last-row / first-column corners of a's first tile row
       (``upper``), two pairs (i in b, j in a) near the mirrored corners (``mirror``), and one of the
-      last rows of a with a row of b (``boundary``).
+      last rows of a with a row of b (``boundary``). Cross-view (the distributed InfoNCE kernels: a
+      row's columns are the other view's rows of EVERY block, the positive only in its own), in each
+      direction (i in a, j in b) and (i in b, j in a), the sides alternating: j at the local index of
+      i's positive, the other block's would-be positive that must count as a plain negative
+      (``would-be``), its neighbours (``pos+1`` / ``pos-1``), the last valid local column of a block,
+      n-1 or the nearest one the rules leave free (``last-col``), and the first, 0 or the nearest free
+      one (``first-col``).
 
     Row R-1 is the positive of row n-1, row 0 of row n and row R-2 of row n-2, so the third rule
     does not admit the seam pairs and the edge pairs as written together. Where the last tile is
@@ -309,9 +315,9 @@ def boundary_probes(rows: int, tile: int, *, blocks: int = 1, cross_view: bool =
         _self_mask_probes(pl, o)
         _positive_probes(pl, o)
         _corner_probes(pl, o)
-    if blocks > 1 and not cross_view:
+    if blocks > 1:
         for a in range(blocks if blocks > 2 else 1):  # each block with the next (two blocks: one pair)
-            _cross_block_probes(pl, a * rows, (a + 1) % blocks * rows)
+            (_cross_block_xview_probes if cross_view else _cross_block_probes)(pl, a * rows, (a + 1) % blocks * rows)
     return (pl.probes, pl.labels) if return_labels else pl.probes
 
 
@@ -332,17 +338,18 @@ class _ProbePlacer:
         b, l = divmod(k, self.R)
         return b * self.R + (l + self.n) % self.R
 
-    def free(self, i: int, j: int) -> bool:
+    def free(self, i: int, j: int, cross_block: bool = False) -> bool:
         total = self.blocks * self.R
         if not (0 <= i < total and 0 <= j < total) or i == j or j == self.pos(i):
             return False
-        if self.cross_view and (i // self.R != j // self.R or (i % self.R >= self.n) == (j % self.R >= self.n)):
+        if self.cross_view and ((i // self.R != j // self.R) != cross_block
+                                or (i % self.R >= self.n) == (j % self.R >= self.n)):
             return False
         return i not in self.taken and j not in self.taken
 
-    def put(self, label, cands) -> bool:
+    def put(self, label, cands, cross_block: bool = False) -> bool:
         for i, j in cands:
-            if self.free(i, j):
+            if self.free(i, j, cross_block):
                 self.taken.update((i, j, self.pos(i), self.pos(j)))
                 self.probes.append((i, j))
                 self.labels.append(label)
@@ -421,6 +428,23 @@ def _cross_block_probes(pl: _ProbePlacer, oa: int, ob: int) -> None:
     pl.put(("cross-block", "mirror"), [(ob + 24 + s, oa + t - 25 - s) for s in range(16)])
     pl.put(("cross-block", "mirror"), [(ob + R - 25 - s, oa + 24 + s) for s in range(16)])
     pl.put(("cross-block", "boundary"), [(oa + R - 5 - s, ob + 64 + s) for s in range(12)])
+
+
+def _cross_block_xview_probes(pl: _ProbePlacer, oa: int, ob: int) -> None:
+    """Cross-view pairs with the row in one block and the column in the other, both directions; local
+    indices count within a view. Rows from the middle of the view, tried in turn (a candidate list
+    like any other here; with it the seeded inputs of tests/test_infonce_dist_cpu.py keep the input
+    conditions sig >= 0.2 and 0.15 <= P_ij <= 0.85, which a row with an unusually strong positive breaks)."""
+    n = pl.n
+    ls = [x for x in (100, 70, 43, 23, 55, 85, 115, 33, 63, 93, 48, 78, 108) if 1 <= x < n - 1]
+    for d, (oi, oj) in enumerate(((oa, ob), (ob, oa))):
+        kinds = [("would-be", [(l, l) for l in ls]), ("pos+1", [(l, l + 1) for l in ls]),
+                 ("pos-1", [(l, l - 1) for l in ls]),
+                 ("last-col", [(l, c) for c in range(n - 1, n - 17, -1) for l in ls]),
+                 ("first-col", [(l, c) for c in range(16) for l in ls])]
+        for k, (name, cands) in enumerate(kinds):
+            v = (k + d) % 2  # the view of row i: both sides occur in both directions
+            pl.put(("cross-block", name), [(oi + v * n + l, oj + (1 - v) * n + c) for l, c in cands], cross_block=True)
 
 
 def plant_pairs(h: torch.Tensor, probes: Sequence[Tuple[int, int]], c: float) -> torch.Tensor:

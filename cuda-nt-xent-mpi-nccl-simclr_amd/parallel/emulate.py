@@ -68,6 +68,34 @@ def emulated_dist_forward_backward(shards: Sequence[torch.Tensor], temperature: 
     return loss, grads
 
 
+def emulated_xview_forward_backward(shards: Sequence[torch.Tensor], temperature: float, *, compute: str = "auto",
+                                    grad_out: float = 1.0) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+    """Distributed cross-view InfoNCE (:mod:`parallel.infonce`) for W virtual ranks on one device:
+    loss of the global batch in pair order and per-rank dL/dh_r for shards h_r = [a_r; b_r]. Every
+    rank's prep writes its slot of the shared ``zq_all`` and its merge its slot of ``lse2_all``."""
+    from .infonce import _CDT, xview_compute, xview_stage_forward
+
+    C = _ext.load()
+    W = len(shards)
+    R, d = shards[0].shape
+    dev = shards[0].device
+    comp = xview_compute(shards[0].dtype, False, compute)
+    plans = [C.get_plan(R, d, W, r, float(temperature), comp, dev.index) for r in range(W)]
+    Rpad = plans[0].rows_pad
+    hs = [x.contiguous() for x in shards]
+    zq_all = torch.empty((W * Rpad, plans[0].ld_k), dtype=_CDT[comp], device=dev)
+    preps = [C.prep(hs[r], plans[r], zq_all[r * Rpad:(r + 1) * Rpad], None) for r in range(W)]  # "all-gather"
+    lse2_all = torch.empty((W * Rpad,), dtype=torch.float32, device=dev)
+    loss = torch.zeros((), dtype=torch.float64, device=dev)
+    cposs = []
+    for r in range(W):
+        share, cpos = xview_stage_forward(C, plans[r], zq_all, preps[r][2], lse2_all)
+        loss = loss + share  # "all-reduce" (fp64 shares)
+        cposs.append(cpos)
+    go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
+    return loss.float(), [C.xview_dist_backward(hs[r], zq_all, preps[r][1], lse2_all, cposs[r], go, plans[r]) for r in range(W)]
+
+
 def emulated_ring_forward_backward(shards: Sequence[torch.Tensor], temperature: float, *, compute: str = "auto",
                                    grad_out: float = 1.0) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """The ring-negatives stage ops (:mod:`parallel.ring`) for W virtual ranks on one device:
