@@ -460,7 +460,11 @@ void launch_pos_rank(DType comp, const void* zq, const Geometry& g, int* rank, f
 // the view-2 rows (launch_lse's `part` layout) into `scratch` (xview_fwd_scratch_bytes, 8-byte
 // aligned, no initialisation needed); a merge launch gives lse2 / cpos ([rows_pad] each, with
 // launch_lse's meaning) and the pairs' loss terms, a one-block launch their fixed-order sum: loss[0].
-// Three launches, deterministic, no atomics.
+// Three launches, deterministic, no atomics. xview_fwd_scratch_bytes = xview_part_bytes (the
+// partials, [g.world * n_pad / 128][rows_pad] float2) + xview_lse_scratch_bytes (the pairs' loss
+// terms), the two buffers of the distributed form below.
+size_t xview_part_bytes(const Geometry& g);
+size_t xview_lse_scratch_bytes(const Geometry& g);
 size_t xview_fwd_scratch_bytes(const Geometry& g);
 void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g, float* lse2, float* cpos,
                       float* loss, void* scratch, hipStream_t stream);
@@ -497,22 +501,20 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
 //     lse2 into this rank's slot of lse2_all (pad rows zeroed) and cpos [Rpad], and loss[0] = this
 //     rank's share sum_i (lse_i - y_ip) / (2N), in fp64: a SUM over the ranks, rounded to fp32 once,
 //     gives the loss (fp32 shares would round W + 1 times, more than the one-GPU loss does). scratch:
-//     xview_dist_lse_scratch_bytes (8-byte aligned, no initialisation needed).
-//   launch_xview_dist_zt  : zt [2][En][W * n_pad] (xview_dist_zt_bytes): view v of slot q transposed
+//     xview_lse_scratch_bytes (8-byte aligned, no initialisation needed).
+//   launch_xview_dist_zt  : zt [2][En][W * n_pad] (xview_zt_bytes): view v of slot q transposed
 //     into columns [q * n_pad, (q + 1) * n_pad), zero padded.
 //   launch_xview_dist_coef: the n_pad x W n_pad coefficient block of ONE side,
 //     G_ij = exp2(y_ij - lse2_i) + exp2(y_ij - lse2_j) - 2 [j = p(i)], into `coef`
-//     (xview_dist_coef_bytes = 4 n_pad W n_pad bytes in every plan; planes as launch_xview_coef),
+//     (xview_coef_bytes = 4 n_pad W n_pad bytes in every plan; planes as launch_xview_coef),
 //     exact zeros outside the valid rows and columns.
 //   launch_xview_dist_dz  : rows [side * n, side * n + n) of the fp32 slab dz [Rpad][dim_n]
 //     (xview_dz_bytes) = G Z over K = planes x W x n_pad (xview_dz_kernel: the residual plane, then
 //     the hi plane, the rank slots ascending inside each).
 // Side 0 then side 1 through the same `coef`, then launch_norm_bwd (whose scale is the global
-// 1 / (2N tau)). No atomics, no host sync: deterministic and capturable.
-size_t xview_dist_part_bytes(const Geometry& g);
-size_t xview_dist_lse_scratch_bytes(const Geometry& g);
-size_t xview_dist_coef_bytes(DType comp, const Geometry& g);
-size_t xview_dist_zt_bytes(DType comp, const Geometry& g);
+// 1 / (2N tau)). No atomics, no host sync: deterministic and capturable. The same kernels as above
+// (one GPU is W = 1 of them, with the column partials and the in-place G^T in place of side 1); the
+// buffer sizes are the functions above, which read g.world.
 void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, int q_lo, int q_hi, int q_skip,
                            float2* part, float* ypos, hipStream_t stream);
 void launch_xview_dist_lse(const float2* part, const float* ypos, const Geometry& g, float* lse2_all, float* cpos,

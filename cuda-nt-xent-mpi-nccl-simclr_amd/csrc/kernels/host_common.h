@@ -26,16 +26,15 @@ void dispatch_gemm(DType t, F&& f) {
   else dispatch_comp(t, f);
 }
 
-// launch_prep's unit rows of a one-rank geometry as the 128 x 128 tile kernels (tile128.h) read
-// them: rows ldb bytes apart, nk K-steps of 128 bytes each. How many rows a kernel reads, and so
-// what row padding it needs, is for its launcher to check.
+// launch_prep's unit rows as the 128 x 128 tile kernels (tile128.h) read them: rows ldb bytes
+// apart, nk K-steps of 128 bytes each. How many rows a kernel reads, of how many ranks, and so what
+// row padding and world it needs, is for its launcher to check.
 struct UnitRows {
   const char* ptr;
   long long ldb;
   int nk;
 };
 inline UnitRows unit_rows(DType comp, const void* zq, const Geometry& g, const std::string& who) {
-  NTXENT_CHECK(g.world == 1, who + ": one rank only (build the geometry with world = 1)");
   NTXENT_CHECK(comp == DType::F32 || comp == DType::F16 || comp == DType::BF16, who + ": fp32 | fp16 | bf16 rows");
   const size_t es = dtype_size(comp), kbytes = (size_t)g.dim_k * es;
   NTXENT_CHECK(kbytes % kKStepBytes == 0 && g.dim_k <= g.ld_k && kbytes >= kKStepBytes,

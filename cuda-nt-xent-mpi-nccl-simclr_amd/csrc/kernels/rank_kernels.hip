@@ -212,6 +212,7 @@ __global__ __launch_bounds__(kTile128Threads) void pos_rank_kernel(const RankPar
 
 void launch_pos_rank(DType comp, const void* zq, const Geometry& g, int* rank, float* pos_cos, float* hard_neg_cos,
                      hipStream_t stream) {
+  NTXENT_CHECK(g.world == 1, "pos_rank: one rank only (build the geometry with world = 1)");
   const UnitRows u = unit_rows(comp, zq, g, "pos_rank");
   dev::RankParams p{};
   p.zq = u.ptr;

@@ -1,60 +1,56 @@
-// Cross-view InfoNCE kernels for gfx950: the CLIP-form two-tower loss of one rank's rows.
+// Cross-view InfoNCE kernels for gfx950: the CLIP-form two-tower loss, rank r of W ranks.
 //
-// Rows are stacked as everywhere else (zq = launch_prep's unit rows, R = 2N, p(i) = (i + N) mod R),
-// but a row's columns are the rows of the OTHER view only, the positive included:
-//   lse_i = log sum_{j : view(j) != view(i)} exp(cos_ij / tau),  loss = 1/R sum_i (lse_i - cos_ip / tau)
-// Only the N x N block S12 = Z1 Z2^T is ever needed: its rows are the view-1 rows' logits and its
-// columns the view-2 rows'. With P_ij = exp(cos_ij / tau - lse_i) the gradient block is
-//   G = P12 + P21^T - 2 I      (N x N; the diagonal, the positives, is the merge's cpos)
-// and (C z)[0:N] = G Z2, (C z)[N:] = G^T Z1.
+// Every rank holds n pairs, stacked as everywhere else ([view 1 (n); view 2 (n); zero pad] =
+// launch_prep's unit rows, rows_pad of them); zq holds the W ranks' rows slot by slot and the global
+// batch in pair order is [a_0; ..; a_{W-1}; b_0; ..; b_{W-1}] (N = W n pairs). A row's columns are the
+// rows of the OTHER view only, the positive included:
+//   lse_i = log sum_{j : view(j) != view(i)} exp(cos_ij / tau),  loss = 1/2N sum_i (lse_i - cos_ip / tau)
+// Per side v the rows are view v of this rank and the columns view 1 - v of every slot; column tile J
+// of a side's n x N block is local tile J % nT of slot J / nT (nT = n_pad / 128), and the positive of
+// local row l is column l of the own slot. With P_ij = exp(cos_ij / tau - lse_i) the gradient block
+// of a side is G_ij = P_ij + P_ji - 2 [j = p(i)], and (C z)[side rows] = G Z(other view).
 //
-//   xview_fwd_kernel  : one 128 x 128 tile of S12 per workgroup, all nT x nT tiles (no symmetry
-//                       in this block), by tile128.h's MFMA loop. Epilogue: negatives-only
-//                       (max, sum exp2) per row for the view-1 rows and per column for the view-2
-//                       rows, reduced in the wave and across the two waves in a fixed order, and
-//                       stored in launch_lse's `part` layout: slot J for the rows, slot I for the
-//                       columns (nT = rows_pad / 256 slots: exactly launch_lse's column tiles).
-//                       Every (slot, row < R) is written exactly once; the diagonal tiles also
-//                       store the pairs' positive logits (ypos), so a pair's positive and its
-//                       negatives come from the same MFMA arithmetic.
-//   xview_lse_kernel  : a thread per positive pair merges the slots of both rows in slot order with
-//                       the positive logit (negatives-only LSE merged with y_pos and the positive
+//   xview_fwd_kernel  : one 128 x 128 tile (side, I, slot q, local tile Jl) per workgroup by
+//                       tile128.h's MFMA loop. Epilogue: negatives-only (max, sum exp2) per row,
+//                       reduced in the wave and across the two waves in a fixed order, and stored in
+//                       launch_lse's `part` layout, slot q * nT + Jl, row side * n + l. Every (slot,
+//                       valid row) is written exactly once, so any split of the slots over launches
+//                       (own slot first, while the others are gathered) gives the same bits; side 0's
+//                       own diagonal tiles also store the pairs' positive logits (ypos), so a pair's
+//                       positive and its negatives come from the same MFMA arithmetic.
+//   xview_lse_kernel  : a thread per positive pair merges the W * nT slots of both rows in slot order
+//                       with the positive logit (negatives-only LSE merged with y_pos and the positive
 //                       coefficient -(sigmoid(lse_neg_i - y) + sigmoid(lse_neg_p - y)), as launch_lse:
-//                       stable when P_ip -> 1); the loss terms are formed in fp64 relative to y_pos.
+//                       stable when P_ip -> 1) into this rank's slot of lse2; the loss terms are
+//                       formed in fp64 relative to y_pos.
 //   xview_loss_kernel : their sum in a fixed order (one block, fp64 tree). No atomics anywhere.
-//   xview_coef_kernel : the same tile GEMM again; the epilogue forms the tile of G from lse2 / cpos
-//                       and stores it once, row-major [N_pad][N_pad] planes in the compute dtype
-//                       (zeros outside N x N): one fp32 plane, or for 16-bit plans G rounded to the
-//                       dtype and the scaled residual of that rounding, so that the MFMA operands
-//                       carry the coefficients to about twice the dtype's mantissa (a gradient of
-//                       equal coefficients is otherwise off by the dtype's rounding of that one
-//                       number). The only N^2 data, 4 N_pad^2 bytes in every plan.
-//   xview_transpose_kernel : Zt[v][e][c] = zq[v N + c][e], both views aligned at column 0 and zero
-//                       padded to N_pad columns and roundup(dim_k, 128) rows (view 2 starts at row
-//                       N of zq, which is usually not tile aligned).
-//   xview_dz_kernel   : out = G Z2, and after xview_gt_kernel has transposed the planes in place,
-//                       G^T Z1: one 128 x 128 output tile per workgroup, K = N_pad, both operands
-//                       streamed K-major by LDS-DMA in the same MFMA loop (tile128.h's, over the
-//                       K-steps of every plane); 16-bit plans run the residual plane, scale the
-//                       accumulators back and run the hi plane. fp32
-//                       output slab. Each output element is one workgroup's fixed-order sum:
-//                       deterministic.
+//   xview_side_coef_kernel : the same tile GEMM again for ONE side; the epilogue forms the tile of G
+//                       from the gathered lse2 and cpos and stores it once, row-major [n_pad][W n_pad]
+//                       planes in the compute dtype (zeros outside the valid rows and columns): one
+//                       fp32 plane, or for 16-bit plans G rounded to the dtype and the scaled residual
+//                       of that rounding, so that the MFMA operands carry the coefficients to about
+//                       twice the dtype's mantissa (a gradient of equal coefficients is otherwise off
+//                       by the dtype's rounding of that one number). The only n N data, 4 n_pad W n_pad
+//                       bytes in every plan. Side 1 swaps the operand roles and so gives the rows of
+//                       G^T directly.
+//   xview_transpose_kernel : Zt[v][e][q n_pad + c] = zq[q rows_pad + v n + c][e] for every slot q,
+//                       both views aligned at column 0 of their slot and zero padded to n_pad columns
+//                       and roundup(dim_k, 128) rows (view 2 starts at row n, usually not tile aligned).
+//   xview_dz_kernel   : a side's rows of out = G Z: one 128 x 128 output tile per workgroup, K =
+//                       W n_pad per plane (slots ascending inside a plane), both operands streamed
+//                       K-major by LDS-DMA in the same MFMA loop (tile128.h's, over the K-steps of
+//                       every plane); 16-bit plans run the residual plane, scale the accumulators back
+//                       and run the hi plane. fp32 output slab. Each output element is one workgroup's
+//                       fixed-order sum: deterministic.
 // launch_norm_bwd (with dot_out) and launch_tau_grad finish the backward as they are.
 //
-// Distributed form (rank r of W, the global batch [a_0; ..; a_{W-1}; b_0; ..; b_{W-1}]): per side v
-// the rows are view v of this rank and the columns view 1 - v of every rank's slot of the gathered
-// rows, so both n x N blocks are computed here and nothing but the rows and the LSE crosses ranks.
-//   xview_dist_fwd_kernel  : tiles (side, I, J), column tile J = local tile J % nT of slot J / nT;
-//                       row partials only, one slot per column tile; the positive is the own slot's
-//                       column of the row's local index. Any split of the slots over launches (own
-//                       slot first, while the others are gathered) gives the same bits.
-//   xview_lse_kernel / xview_loss_kernel : as above over W * nT slots into this rank's slot of
-//                       lse2_all; the rank's loss share stays in fp64.
-//   xview_dist_coef_kernel : ONE side's n_pad x W n_pad block G_ij = P_ij + P_ji - 2 [j = p(i)], P_ji
-//                       from the gathered LSE; side 1 swaps the operand roles and so gives the rows of
-//                       G^T directly (no in-place transpose, no gradient collective).
-//   xview_transpose_kernel : Zt[v][e][q n_pad + c] for every slot q, made locally from the gathered rows.
-//   xview_dz_kernel   : the same kernel with K = W n_pad per plane (slots ascending inside a plane).
+// One GPU is W = 1, r = 0 of the same kernels, except in two places where one block S12 = Z1 Z2^T
+// serves both sides:
+//   - the forward runs side 0's nT x nT tiles only, with kCols: the tile's columns are the view-2
+//     rows' logits, so the epilogue also reduces (max, sum exp2) per column and stores them as the
+//     view-2 rows' partials, slot I (half the forward FLOPs of two sides);
+//   - the backward stores G once (side 0) and xview_gt_kernel transposes the planes in place between
+//     the two dZ products, instead of a second coefficient pass.
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
 #include "host_common.h"
@@ -66,19 +62,23 @@ namespace dev {
 constexpr int kXvTile = kTile128;
 constexpr int kXvThreads = kTile128Threads;
 
+// zq holds W slots of rows_pad rows. With n + n_pad <= rows_pad no 128-row stage leaves its slot.
 struct XvParams {
-  const char* zq;   // [rows_pad][ldb bytes] unit rows (zero K padding, zero pad rows)
-  long long ldb;    // row stride in bytes
-  int n_half;       // N
+  const char* zq;     // [world * rows_pad][ldb bytes] unit rows (zero K padding, zero pad rows)
+  long long ldb;      // row stride in bytes
+  int n;              // pairs per rank
   int rows_pad;
-  int nk;           // 128-byte K-steps per row of zq
-  int nT;           // 128-row tiles per side of the N x N block
-  float scale2;     // log2(e) / tau: cosine -> logit in log2 units
-  float2* part;     // forward: [nT][rows_pad] (launch_lse's layout)
-  float* ypos;      // forward: [>= N] positive logits of the pairs (log2 units), written
-  const float* lse2;  // coefficient pass: [rows_pad] LSE (log2 units, positive included)
-  const float* cpos;  //                   [rows_pad] positive coefficient
-  char* gbuf;       // [planes][N_pad][ldg bytes] G in the compute dtype (16-bit: residual plane, hi plane)
+  int nk;             // 128-byte K-steps per row of zq
+  int nT;             // n_pad / 128: 128-row tiles per view of a slot
+  int world, rank;
+  int q_lo, nq, q_skip;  // forward: the launch's column slots, nq of them from q_lo on, q_skip left out
+  int side;           // coefficient pass: the side
+  float scale2;       // log2(e) / tau: cosine -> logit in log2 units
+  float2* part;       // forward: [world * nT][rows_pad] (launch_lse's layout), row side * n + l
+  float* ypos;        // forward: [>= n] positive logits of the pairs (log2 units), written
+  const float* lse2;  // coefficient pass: [world * rows_pad] gathered LSE (log2 units, positive included)
+  const float* cpos;  //                   [rows_pad] positive coefficients of this rank's rows
+  char* gbuf;         // [planes][n_pad][ldg bytes] G in the compute dtype (16-bit: residual plane, hi plane)
   long long ldg;
   long long plane_bytes;
 };
@@ -86,19 +86,23 @@ struct XvParams {
 // runs it first and scales its accumulators back (a power of two: exact) before the hi plane.
 constexpr float kXvLoScale = 2048.f;
 
-// acc = tile (I, J) of Z1 Z2^T: rows I * 128 .. of zq against rows N + J * 128 .. of zq. Ends with a
-// block barrier: the caller's epilogue may reuse the staging images.
+// acc = tile (I, Jl of slot q) of side `side`: rows side * n + I * 128 .. of the own slot against
+// rows (1 - side) * n + Jl * 128 .. of slot q. Ends with a block barrier: the caller's epilogue may
+// reuse the staging images.
 template <typename T>
-__device__ __forceinline__ void xv_tile_gemm(const XvParams& p, int I, int J, lds_char* lds, f32x4 (&acc)[4][4]) {
-  const char* arow = p.zq + (long long)I * kXvTile * p.ldb;
-  const char* brow = p.zq + ((long long)p.n_half + (long long)J * kXvTile) * p.ldb;
+__device__ __forceinline__ void xv_tile_gemm(const XvParams& p, int side, int I, int q, int Jl, lds_char* lds,
+                                             f32x4 (&acc)[4][4]) {
+  const char* arow = p.zq + ((long long)p.rank * p.rows_pad + (long long)side * p.n + (long long)I * kXvTile) * p.ldb;
+  const char* brow = p.zq + ((long long)q * p.rows_pad + (long long)(1 - side) * p.n + (long long)Jl * kXvTile) * p.ldb;
   tile128_gemm<T>(
       lds, p.nk, [&](int k) { return Tile128Src{arow + (long long)k * kKStepBytes, p.ldb}; },
       [&](int k) { return Tile128Src{brow + (long long)k * kKStepBytes, p.ldb}; }, false, Tile128Plain{}, acc);
 }
 
-// ---- forward: LSE partials of the tile's rows (view 1) and columns (view 2) -----------------
-template <typename T>
+// ---- forward: LSE partials of the tile's rows, slot q * nT + Jl -------------------------------------
+// kCols (one GPU: world 1, side 0's tiles): also of its columns, the other view's rows, slot I.
+// Without it the other view's rows get theirs from the other side's tiles.
+template <typename T, bool kCols>
 __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p) {
   // ONE __shared__ object (staging ring, reused by the epilogue)
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
@@ -106,25 +110,33 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int I = b / p.nT, J = b - I * p.nT;
-  const int N = p.n_half;
+  const int ncol = p.nq * p.nT, per_side = p.nT * ncol;
+  const int side = b / per_side, rem = b - side * per_side;
+  const int I = rem / ncol, jj = rem - I * ncol;
+  int q = p.q_lo + jj / p.nT;
+  const int Jl = jj % p.nT;
+  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
+  const int n = p.n;
+  const bool own = q == p.rank;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, I, J, lds, acc);
+  xv_tile_gemm<T>(p, side, I, q, Jl, lds, acc);
 
-  // epilogue LDS: per-wave-column row (max, sum) | per-wave-row column (max, sum)
+  // epilogue LDS: per-wave-column row (max, sum) | kCols: per-wave-row column (max, sum)
   float* s_rm = reinterpret_cast<float*>(smem);  // [2][128]
   float* s_rs = s_rm + 2 * kXvTile;
   float* s_cm = s_rs + 2 * kXvTile;
   float* s_cs = s_cm + 2 * kXvTile;
 
-  int cj[4];
-  float cm[4], cs[4];
+  int cl[4];
+  [[maybe_unused]] float cm[4], cs[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
-    cj[ni] = J * kXvTile + 64 * wc + 16 * ni + r16;
-    cm[ni] = kNegInf;
-    cs[ni] = 0.f;
+    cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+    if constexpr (kCols) {
+      cm[ni] = kNegInf;
+      cs[ni] = 0.f;
+    }
   }
   // pass 1: logits (log2 units; -inf for what is no negative) and the maxima
   float rmx[4][4];
@@ -132,28 +144,30 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int gi = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+      const int li = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
       float m = kNegInf;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
-        // a view-1 tile row at or beyond N is a view-2 row and a view-2 tile row at or beyond N is a
-        // pad row (cosine 0) or nothing of this problem: masked by index. The positive (the diagonal
-        // of the block) joins in xview_lse_kernel.
-        const bool in = (gi < N) & (cj[ni] < N);
-        const bool ok = in & (cj[ni] != gi);
+        // local rows and columns at or beyond n are the other view's rows or slot padding: masked by
+        // index. The positive is the own slot's column of the same local index and nothing else; it
+        // joins in xview_lse_kernel.
+        const bool in = (li < n) & (cl[ni] < n);
+        const bool pos = own & (cl[ni] == li);
         const float yv = acc[mi][ni][r] * p.scale2;
         // the pair's positive logit from the same MFMA sum as its negatives (one lane of one tile
         // per pair): rows whose cosines are equal then have exactly equal logits
-        if (in & (cj[ni] == gi)) p.ypos[gi] = yv;
-        const float y = ok ? yv : kNegInf;
+        if (in & pos & (side == 0)) p.ypos[li] = yv;
+        const float y = (in & !pos) ? yv : kNegInf;
         acc[mi][ni][r] = y;
         m = fmaxf(m, y);
-        cm[ni] = fmaxf(cm[ni], y);
+        if constexpr (kCols) cm[ni] = fmaxf(cm[ni], y);
       }
       rmx[mi][r] = row16_max(m);
     }
+  if constexpr (kCols) {
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) cm[ni] = xrow_max(cm[ni]);
+    for (int ni = 0; ni < 4; ++ni) cm[ni] = xrow_max(cm[ni]);
+  }
   // pass 2: sums of exp2 against the maxima
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
@@ -167,7 +181,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
         const float y = acc[mi][ni][r];
         const bool ok = y != kNegInf;
         s += ok ? fast_exp2(y - mr) : 0.f;
-        cs[ni] += ok ? fast_exp2(y - cm[ni]) : 0.f;
+        if constexpr (kCols) cs[ni] += ok ? fast_exp2(y - cm[ni]) : 0.f;
       }
       s = row16_sum(s);
       if (r16 == 0) {
@@ -175,28 +189,30 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
         s_rs[wc * kXvTile + rt] = s;
       }
     }
+  if constexpr (kCols) {
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    cs[ni] = xrow_sum(cs[ni]);
-    if (g == 0) {
-      const int ct = 64 * wc + 16 * ni + r16;
-      s_cm[wr * kXvTile + ct] = cm[ni];
-      s_cs[wr * kXvTile + ct] = cs[ni];
+    for (int ni = 0; ni < 4; ++ni) {
+      cs[ni] = xrow_sum(cs[ni]);
+      if (g == 0) {
+        const int ct = 64 * wc + 16 * ni + r16;
+        s_cm[wr * kXvTile + ct] = cm[ni];
+        s_cs[wr * kXvTile + ct] = cs[ni];
+      }
     }
   }
   __syncthreads();
-  // threads [0, 128): the tile's rows -> slot J; [128, 256): its columns -> slot I
-  {
-    const bool col = tid >= kXvTile;
+  // threads [0, 128): the tile's rows -> slot q * nT + Jl; kCols, [128, 256): its columns -> slot I
+  const bool col = kCols && tid >= kXvTile;
+  if (kCols || tid < kXvTile) {
     const int t = tid & (kXvTile - 1);
     const float* sm = col ? s_cm : s_rm;
     const float* ss = col ? s_cs : s_rs;
     float m = sm[t], s = ss[t];
     lse_merge(m, s, sm[kXvTile + t], ss[kXvTile + t]);
-    const int idx = (col ? J : I) * kXvTile + t;  // index within the view
-    if (idx < N) {
-      const long long slot = col ? I : J;
-      p.part[slot * p.rows_pad + (col ? N + idx : idx)] = make_float2(m, s);
+    const int idx = (col ? Jl : I) * kXvTile + t;  // index within the view
+    if (idx < n) {
+      const long long slot = col ? I : (long long)q * p.nT + Jl;
+      p.part[slot * p.rows_pad + (col ? 1 - side : side) * n + idx] = make_float2(m, s);
     }
   }
 }
@@ -271,19 +287,22 @@ __global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double*
   }
 }
 
-// ---- backward: the tile of G = P12 + P21^T - 2 I, stored once ---------------------------------
+// ---- backward: tile (I, J) of one side's n_pad x W n_pad block G, stored once ----------------------
 template <typename T>
-__global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p) {
+__global__ __launch_bounds__(kXvThreads) void xview_side_coef_kernel(const XvParams p) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int I = b / p.nT, J = b - I * p.nT;
-  const int N = p.n_half;
+  const int ncol = p.world * p.nT;
+  const int I = b / ncol, J = b - I * ncol;
+  const int q = J / p.nT, Jl = J - q * p.nT;
+  const int n = p.n, side = p.side;
+  const bool own = q == p.rank;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, I, J, lds, acc);
+  xv_tile_gemm<T>(p, side, I, q, Jl, lds, acc);
 
   // the tile's planes in the compute dtype, row-major [128][128] each, over the staging images
   // (64 KiB): fp32 plans one plane, G; 16-bit plans the residual plane (G - hi) * 2^11, then hi =
@@ -291,28 +310,30 @@ __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p
   constexpr bool kSplit = sizeof(T) == 2;
   constexpr int kPlaneElems = kXvTile * kXvTile;
   T* s_g = reinterpret_cast<T*>(smem);
-  int cj[4];
+  const float* lrow = p.lse2 + (long long)p.rank * p.rows_pad + side * n;
+  const float* lcol = p.lse2 + (long long)q * p.rows_pad + (1 - side) * n;
+  int cl[4];
   float lc[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
-    cj[ni] = J * kXvTile + 64 * wc + 16 * ni + r16;
-    lc[ni] = cj[ni] < N ? p.lse2[N + cj[ni]] : 0.f;
+    cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+    lc[ni] = cl[ni] < n ? lcol[cl[ni]] : 0.f;
   }
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int rt = 64 * wr + 16 * mi + 4 * g + r;
-      const int gi = I * kXvTile + rt;
-      const float li = gi < N ? p.lse2[gi] : 0.f;
-      const float cp = gi < N ? p.cpos[gi] : 0.f;
+      const int li = I * kXvTile + rt;
+      const float lr = li < n ? lrow[li] : 0.f;
+      const float cp = li < n ? p.cpos[side * n + li] : 0.f;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const float y = acc[mi][ni][r] * p.scale2;
-        const bool ok = (gi < N) & (cj[ni] < N);
-        const float c = fast_exp2(y - li) + fast_exp2(y - lc[ni]);
-        // selects, not products: outside N x N the exponentials may overflow
-        const float v = ok ? (cj[ni] == gi ? cp : c) : 0.f;
+        const bool ok = (li < n) & (cl[ni] < n);
+        const float c = fast_exp2(y - lr) + fast_exp2(y - lc[ni]);
+        // selects, not products: outside the valid rows and columns the exponentials may overflow
+        const float v = ok ? ((own & (cl[ni] == li)) ? cp : c) : 0.f;
         const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
         const T hi = from_f32<T>(v);
         if constexpr (kSplit) {
@@ -329,8 +350,8 @@ __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p
   constexpr int kCpp = kCpr * kXvTile;  // chunks per plane
   char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
 #pragma unroll
-  for (int q = 0; q < kTile128Lds / 16 / kXvThreads; ++q) {
-    const int idx = q * kXvThreads + tid;
+  for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
+    const int idx = c * kXvThreads + tid;
     const int plane = idx / kCpp, in = idx - plane * kCpp;
     const int row = in / kCpr, cc = in - row * kCpr;
     const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
@@ -338,7 +359,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_coef_kernel(const XvParams p
   }
 }
 
-// ---- Zt[v][e][q slot_cols + c] = zq[q slot_rows + v N + c][e] (blockIdx.z = 2 q + v; one GPU: q = 0) ----
+// ---- Zt[v][e][q slot_cols + c] = zq[q slot_rows + v N + c][e] (blockIdx.z = 2 q + v) ---------------
 template <typename T>
 __global__ __launch_bounds__(256) void xview_transpose_kernel(const T* __restrict__ zq, T* __restrict__ zt, int N,
                                                               int dim_k, long long ldk, int En, long long ldz,
@@ -391,7 +412,7 @@ __global__ __launch_bounds__(256) void xview_gt_kernel(T* __restrict__ gbuf, lon
 
 // ---- out = A Z^T-rows: G Z2 (side 0, A = G) | G^T Z1 (side 1, A = G^T) ----------------------------
 struct XvDzParams {
-  const char* gbuf;  // [planes][N_pad][ldg bytes]: G, or G^T after xview_gt_kernel
+  const char* gbuf;  // [planes][n_pad][ldg bytes]: the side's G (one GPU, side 1: G^T after xview_gt_kernel)
   long long ldg;
   long long plane_bytes;
   int planes;        // 1, or 2: the residual plane (scaled by kXvLoScale), then the hi plane
@@ -400,7 +421,7 @@ struct XvDzParams {
   int En;            // roundup(dim_k, 128)
   int n_half;
   int side;          // the view whose rows are written; B is the other view's Zt
-  int nk;            // 128-byte K-steps over N_pad (per plane)
+  int nk;            // 128-byte K-steps over W n_pad (per plane)
   float* out;        // [rows_pad][ldo]
   long long ldo;
 };
@@ -453,290 +474,158 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
     }
 }
 
-// ---- distributed form: this rank's rows against the gathered rows of every rank -------------------
-// zq_all holds W slots of rows_pad rows ([view 1 (n); view 2 (n); zero pad]). Side v: the rows are
-// view v of slot `rank`, the columns view 1 - v of the slots; column tile J of a side's n x N block
-// is local tile J % nT of slot J / nT. With n + n_pad <= rows_pad no 128-row stage leaves its slot.
-struct XvDistParams {
-  const char* zq;     // [world * rows_pad][ldb bytes]
-  long long ldb;
-  int n;              // pairs per rank
-  int rows_pad;
-  int nk;
-  int nT;             // n_pad / 128
-  int world, rank;
-  int q_lo, nq, q_skip;  // forward: the launch's column slots, nq of them from q_lo on, q_skip left out
-  int side;           // coefficient pass: the side
-  float scale2;
-  float2* part;       // forward: [world * nT][rows_pad], row side * n + l
-  float* ypos;        // forward: [>= n] positive logits of the pairs, written (side 0's own diagonal)
-  const float* lse2;  // coefficient pass: [world * rows_pad] gathered LSE
-  const float* cpos;  //                   [rows_pad] positive coefficients of this rank's rows
-  char* gbuf;         // [planes][n_pad][ldg bytes]
-  long long ldg;
-  long long plane_bytes;
-};
-
-// acc = tile (I, Jl of slot q) of side `side`. Ends with a block barrier.
-template <typename T>
-__device__ __forceinline__ void xv_dist_gemm(const XvDistParams& p, int side, int I, int q, int Jl, lds_char* lds,
-                                             f32x4 (&acc)[4][4]) {
-  const char* arow = p.zq + ((long long)p.rank * p.rows_pad + (long long)side * p.n + (long long)I * kXvTile) * p.ldb;
-  const char* brow = p.zq + ((long long)q * p.rows_pad + (long long)(1 - side) * p.n + (long long)Jl * kXvTile) * p.ldb;
-  tile128_gemm<T>(
-      lds, p.nk, [&](int k) { return Tile128Src{arow + (long long)k * kKStepBytes, p.ldb}; },
-      [&](int k) { return Tile128Src{brow + (long long)k * kKStepBytes, p.ldb}; }, false, Tile128Plain{}, acc);
-}
-
-// Forward: negatives-only (max, sum exp2) of the tile's rows, slot q * nT + Jl. Rows only: the
-// other view's rows get theirs from the other side's tiles.
-template <typename T>
-__global__ __launch_bounds__(kXvThreads) void xview_dist_fwd_kernel(const XvDistParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
-  lds_char* lds = (lds_char*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int ncol = p.nq * p.nT, per_side = p.nT * ncol;
-  const int side = b / per_side, rem = b - side * per_side;
-  const int I = rem / ncol, jj = rem - I * ncol;
-  int q = p.q_lo + jj / p.nT;
-  const int Jl = jj % p.nT;
-  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
-  const int n = p.n;
-  const bool own = q == p.rank;
-
-  f32x4 acc[4][4];
-  xv_dist_gemm<T>(p, side, I, q, Jl, lds, acc);
-
-  float* s_rm = reinterpret_cast<float*>(smem);  // [2][128] per-wave-column row (max, sum)
-  float* s_rs = s_rm + 2 * kXvTile;
-  int cl[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
-  float rmx[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int li = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
-      float m = kNegInf;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        // local rows and columns at or beyond n are the other view's rows or slot padding: masked by
-        // index. The positive is the own slot's column of the same local index and nothing else.
-        const bool in = (li < n) & (cl[ni] < n);
-        const bool pos = own & (cl[ni] == li);
-        const float yv = acc[mi][ni][r] * p.scale2;
-        if (in & pos & (side == 0)) p.ypos[li] = yv;
-        const float y = (in & !pos) ? yv : kNegInf;
-        acc[mi][ni][r] = y;
-        m = fmaxf(m, y);
-      }
-      rmx[mi][r] = row16_max(m);
-    }
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rt = 64 * wr + 16 * mi + 4 * g + r;
-      const float mr = rmx[mi][r];
-      float s = 0.f;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const float y = acc[mi][ni][r];
-        s += y != kNegInf ? fast_exp2(y - mr) : 0.f;
-      }
-      s = row16_sum(s);
-      if (r16 == 0) {
-        s_rm[wc * kXvTile + rt] = mr;
-        s_rs[wc * kXvTile + rt] = s;
-      }
-    }
-  __syncthreads();
-  if (tid < kXvTile) {
-    float m = s_rm[tid], s = s_rs[tid];
-    lse_merge(m, s, s_rm[kXvTile + tid], s_rs[kXvTile + tid]);
-    const int li = I * kXvTile + tid;
-    if (li < n) p.part[((long long)q * p.nT + Jl) * p.rows_pad + side * n + li] = make_float2(m, s);
-  }
-}
-
-// Coefficient pass of one side: tile (I, J) of the n_pad x W n_pad block, stored as xview_coef_kernel
-// stores its tile (column J * 128 of the planes' rows).
-template <typename T>
-__global__ __launch_bounds__(kXvThreads) void xview_dist_coef_kernel(const XvDistParams p) {
-  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
-  lds_char* lds = (lds_char*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int ncol = p.world * p.nT;
-  const int I = b / ncol, J = b - I * ncol;
-  const int q = J / p.nT, Jl = J - q * p.nT;
-  const int n = p.n, side = p.side;
-  const bool own = q == p.rank;
-
-  f32x4 acc[4][4];
-  xv_dist_gemm<T>(p, side, I, q, Jl, lds, acc);
-
-  constexpr bool kSplit = sizeof(T) == 2;
-  constexpr int kPlaneElems = kXvTile * kXvTile;
-  T* s_g = reinterpret_cast<T*>(smem);
-  const float* lrow = p.lse2 + (long long)p.rank * p.rows_pad + side * n;
-  const float* lcol = p.lse2 + (long long)q * p.rows_pad + (1 - side) * n;
-  int cl[4];
-  float lc[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
-    lc[ni] = cl[ni] < n ? lcol[cl[ni]] : 0.f;
-  }
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rt = 64 * wr + 16 * mi + 4 * g + r;
-      const int li = I * kXvTile + rt;
-      const float lr = li < n ? lrow[li] : 0.f;
-      const float cp = li < n ? p.cpos[side * n + li] : 0.f;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const float y = acc[mi][ni][r] * p.scale2;
-        const bool ok = (li < n) & (cl[ni] < n);
-        const float c = fast_exp2(y - lr) + fast_exp2(y - lc[ni]);
-        // selects, not products: outside the valid rows and columns the exponentials may overflow
-        const float v = ok ? ((own & (cl[ni] == li)) ? cp : c) : 0.f;
-        const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
-        const T hi = from_f32<T>(v);
-        if constexpr (kSplit) {
-          s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
-          s_g[kPlaneElems + at] = hi;
-        } else {
-          s_g[at] = hi;
-        }
-      }
-    }
-  __syncthreads();
-  constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
-  constexpr int kCpp = kCpr * kXvTile;
-  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
-#pragma unroll
-  for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
-    const int idx = c * kXvThreads + tid;
-    const int plane = idx / kCpp, in = idx - plane * kCpp;
-    const int row = in / kCpr, cc = in - row * kCpr;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
-    *reinterpret_cast<u32x4*>(gt + plane * p.plane_bytes + (long long)row * p.ldg + cc * 16) = v;
-  }
-}
-
 }  // namespace dev
 
 namespace {
 inline int xv_npad(const Geometry& g) { return roundup(g.rows / 2, dev::kXvTile); }
 inline int xv_en(const Geometry& g) { return roundup(g.dim_k, dev::kXvTile); }
+inline int xv_planes(DType comp) { return comp == DType::F32 ? 1 : 2; }
 
-// the unit rows as the tile GEMM reads them (zq may be null: the checks alone)
-UnitRows xv_check(DType comp, const void* zq, const Geometry& g, const char* who) {
+// The gathered rows [world * rows_pad][ld_k] as the tile kernels read them (zq may be null: the checks
+// alone). A row stage reads 128 rows from local row side * n + I * 128 of the own slot, a column stage
+// from (1 - side) * n + Jl * 128 of slot q: at most local row n + n_pad of a slot, so with n + n_pad <=
+// rows_pad no stage reads beyond its slot, and none beyond the world * rows_pad rows of the buffer.
+dev::XvParams xv_params(DType comp, const void* zq, const Geometry& g, const std::string& who) {
   const UnitRows u = unit_rows(comp, zq, g, who);
+  NTXENT_CHECK(g.world >= 1 && g.rank >= 0 && g.rank < g.world, who + ": bad world / rank");
+  NTXENT_CHECK(u.ldb % 16 == 0, who + ": geometry does not pad K to 128 bytes");
   const int n = g.rows / 2, np = xv_npad(g);
-  // the tile GEMM reads rows [0, N_pad) and [N, N + N_pad) of zq; the partials hold rows_pad / 256
-  // slots, which must be the N_pad / 128 tiles per side
-  NTXENT_CHECK(np <= g.rows_pad && n + np <= g.rows_pad && g.col_tiles == np / dev::kXvTile && u.ldb % 16 == 0,
-               std::string(who) + ": geometry does not pad rows to 256");
-  return u;
-}
-
-dev::XvParams xv_params(const UnitRows& u, const Geometry& g) {
+  NTXENT_CHECK(n + np <= g.rows_pad, who + ": a 128-row stage would leave its rank slot");
   dev::XvParams p{};
   p.zq = u.ptr;
   p.ldb = u.ldb;
-  p.n_half = g.rows / 2;
+  p.n = n;
   p.rows_pad = g.rows_pad;
   p.nk = u.nk;
-  p.nT = xv_npad(g) / dev::kXvTile;
+  p.nT = np / dev::kXvTile;
+  p.world = g.world;
+  p.rank = g.rank;
+  p.nq = g.world;
+  p.q_skip = -1;
   p.scale2 = g.inv_temp * dev::kLog2e;
   return p;
 }
+
+// One GPU: one rank, whose partials are launch_lse's: rows_pad / 256 slots, which must be the
+// n_pad / 128 tiles per side.
+dev::XvParams xv_params_one(DType comp, const void* zq, const Geometry& g, const std::string& who) {
+  NTXENT_CHECK(g.world == 1, who + ": one rank only (build the geometry with world = 1)");
+  const int n = g.rows / 2, np = xv_npad(g);
+  NTXENT_CHECK(np <= g.rows_pad && n + np <= g.rows_pad && g.col_tiles == np / dev::kXvTile &&
+                   ((size_t)g.ld_k * dtype_size(comp)) % 16 == 0,
+               who + ": geometry does not pad rows to 256");
+  return xv_params(comp, zq, g, who);
+}
+
+// Merge of the world * nT slots into this rank's slot of lse2_all and cpos, then the loss terms' sum
+// over the global row count: loss[0] in fp32, or (loss null) share64[0].
+void xv_lse_loss(const float2* part, const float* ypos, const Geometry& g, float* lse2_all, float* cpos, double* lpair,
+                 float* loss, double* share64, hipStream_t stream) {
+  const int n = g.rows / 2, nslots = g.world * (xv_npad(g) / dev::kXvTile);
+  hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
+                     ypos, lse2_all + (size_t)g.rank * g.rows_pad, cpos, lpair, n, g.rows_pad, nslots);
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n,
+                     (double)g.global_rows, loss, share64);
+}
+
+void xv_launch_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream) {
+  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
+  dispatch_comp(comp, [&](auto tc) {
+    using Tc = decltype(tc);
+    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2 * g.world), dim3(256), 0, stream,
+                       static_cast<const Tc*>(zq_all), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
+                       (long long)g.world * np, (long long)g.rows_pad, (long long)np);
+  });
+}
+
+void xv_launch_coef(DType comp, dev::XvParams p, const Geometry& g, int side, const float* lse2_all,
+                    const float* cpos, void* coef, hipStream_t stream) {
+  const int np = xv_npad(g);
+  p.side = side;
+  p.lse2 = lse2_all;
+  p.cpos = cpos;
+  p.gbuf = static_cast<char*>(coef);
+  p.ldg = (long long)g.world * np * (long long)dtype_size(comp);
+  p.plane_bytes = (long long)np * p.ldg;
+  const int ntiles = p.nT * g.world * p.nT;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_side_coef_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+  });
+}
+
+// xview_dz_kernel's arguments with K = world * n_pad per plane: the planes' rows and Zt's rows both
+// hold the rank slots side by side, so a plane's K-steps run through the slots in ascending order.
+// The dZ tiles write columns [0, En) of rows [side * n, side * n + n) of the [rows_pad][dim_n] slab.
+dev::XvDzParams xv_dz_params(DType comp, const void* coef, const void* zt, const Geometry& g, float* dz,
+                             const std::string& who) {
+  const size_t es = dtype_size(comp);
+  const int np = xv_npad(g), en = xv_en(g);
+  NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, who + ": dim_n < roundup(dim_k, 128)");
+  dev::XvDzParams q{};
+  q.gbuf = static_cast<const char*>(coef);
+  q.ldg = (long long)g.world * np * (long long)es;
+  q.plane_bytes = (long long)np * q.ldg;
+  q.planes = xv_planes(comp);
+  q.zt = static_cast<const char*>(zt);
+  q.ldz = q.ldg;
+  q.En = en;
+  q.n_half = g.rows / 2;
+  q.nk = (int)((size_t)q.ldg / kKStepBytes);
+  q.out = dz;
+  q.ldo = g.dim_n;
+  return q;
+}
 }  // namespace
 
-static size_t xv_part_bytes(const Geometry& g) { return (size_t)g.col_tiles * g.rows_pad * sizeof(float2); }
-size_t xview_fwd_scratch_bytes(const Geometry& g) { return xv_part_bytes(g) + (size_t)(g.rows / 2) * sizeof(double); }
-static int xv_planes(DType comp) { return comp == DType::F32 ? 1 : 2; }
-// 4 N_pad^2 bytes in every plan: 16-bit plans hold two planes, so their coefficients take as much
-// as one fp32 square would (twice a single 16-bit G). The caller keeps the peak down by releasing
-// zq before the dZ slab and coef / zt before dh, not by a smaller block.
-size_t xview_coef_bytes(DType comp, const Geometry& g) {
-  return (size_t)xv_planes(comp) * xv_npad(g) * xv_npad(g) * dtype_size(comp);
+size_t xview_part_bytes(const Geometry& g) {
+  return (size_t)g.world * (xv_npad(g) / dev::kXvTile) * g.rows_pad * sizeof(float2);
 }
-size_t xview_zt_bytes(DType comp, const Geometry& g) { return (size_t)2 * xv_en(g) * xv_npad(g) * dtype_size(comp); }
+size_t xview_lse_scratch_bytes(const Geometry& g) { return (size_t)(g.rows / 2) * sizeof(double); }
+size_t xview_fwd_scratch_bytes(const Geometry& g) { return xview_part_bytes(g) + xview_lse_scratch_bytes(g); }
+// 4 n_pad W n_pad bytes in every plan: 16-bit plans hold two planes, so their coefficients take as
+// much as one fp32 block would (twice a single 16-bit G). One side at a time; the caller keeps the
+// peak down by releasing zq before the dZ slab and coef / zt before dh, not by a smaller block.
+size_t xview_coef_bytes(DType comp, const Geometry& g) {
+  return (size_t)xv_planes(comp) * xv_npad(g) * g.world * xv_npad(g) * dtype_size(comp);
+}
+size_t xview_zt_bytes(DType comp, const Geometry& g) {
+  return (size_t)2 * xv_en(g) * g.world * xv_npad(g) * dtype_size(comp);
+}
 size_t xview_dz_bytes(const Geometry& g) { return (size_t)g.rows_pad * g.dim_n * sizeof(float); }
 
+// ---- one GPU -----------------------------------------------------------------------------------------
 void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g, float* lse2, float* cpos,
                       float* loss, void* scratch, hipStream_t stream) {
   NTXENT_CHECK(zq && ypos && lse2 && cpos && loss && scratch, "xview_fwd: null buffer");
-  dev::XvParams p = xv_params(xv_check(comp, zq, g, "xview_fwd"), g);
+  dev::XvParams p = xv_params_one(comp, zq, g, "xview_fwd");
   // scratch: the partials [nT][rows_pad] (every entry that is read is written), then the pairs'
   // loss terms [N] (fp64; the partials are a multiple of 8 bytes)
-  float2* part = static_cast<float2*>(scratch);
-  double* lpair = reinterpret_cast<double*>(static_cast<char*>(scratch) + xv_part_bytes(g));
-  p.part = part;
+  p.part = static_cast<float2*>(scratch);
   p.ypos = ypos;
-  const int ntiles = p.nT * p.nT;
+  double* lpair = reinterpret_cast<double*>(static_cast<char*>(scratch) + xview_part_bytes(g));
+  // side 0's tiles alone: their columns give the view-2 rows' partials
   dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+    hipLaunchKernelGGL((dev::xview_fwd_kernel<decltype(tc), true>), dim3(p.nT * p.nT), dim3(dev::kXvThreads), 0, stream, p);
   });
-  const int n = g.rows / 2;
-  hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
-                     ypos, lse2, cpos, lpair, n, g.rows_pad, p.nT);
-  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n, 2.0 * (double)n, loss,
-                     (double*)nullptr);
+  xv_lse_loss(p.part, ypos, g, lse2, cpos, lpair, loss, nullptr, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_coef(DType comp, const void* zq, const float* lse2, const float* cpos, const Geometry& g, void* coef,
-                        void* zt, hipStream_t stream) {
+                       void* zt, hipStream_t stream) {
   NTXENT_CHECK(zq && lse2 && cpos && coef && zt, "xview_coef: null buffer");
-  const size_t es = dtype_size(comp);
-  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
-  dev::XvParams p = xv_params(xv_check(comp, zq, g, "xview_coef"), g);
-  p.lse2 = lse2;
-  p.cpos = cpos;
-  p.gbuf = static_cast<char*>(coef);
-  p.ldg = (long long)np * (long long)es;
-  p.plane_bytes = (long long)np * p.ldg;
-  const int ntiles = p.nT * p.nT;
-  dispatch_comp(comp, [&](auto tc) {
-    using Tc = decltype(tc);
-    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2), dim3(256), 0, stream,
-                       static_cast<const Tc*>(zq), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
-                       (long long)np, 0LL, 0LL);
-    hipLaunchKernelGGL((dev::xview_coef_kernel<Tc>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
-  });
+  const dev::XvParams p = xv_params_one(comp, zq, g, "xview_coef");
+  xv_launch_zt(comp, zq, g, zt, stream);
+  xv_launch_coef(comp, p, g, 0, lse2, cpos, coef, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream) {
-  xv_check(comp, nullptr, g, "xview_dz");
+  xv_params_one(comp, nullptr, g, "xview_dz");
   NTXENT_CHECK(coef && zt && dz, "xview_dz: null buffer");
-  const size_t es = dtype_size(comp);
-  const int np = xv_npad(g), en = xv_en(g);
-  // the dZ tiles write columns [0, En) of rows [0, R) of the [rows_pad][dim_n] slab
-  NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, "xview_dz: dim_n < roundup(dim_k, 128)");
-  dev::XvDzParams q{};
-  q.gbuf = static_cast<const char*>(coef);
-  q.ldg = (long long)np * (long long)es;
-  q.plane_bytes = (long long)np * q.ldg;
-  q.planes = xv_planes(comp);
-  q.zt = static_cast<const char*>(zt);
-  q.ldz = (long long)np * (long long)es;
-  q.En = en;
-  q.n_half = g.rows / 2;
-  q.nk = (int)((size_t)np * es / kKStepBytes);
-  q.out = dz;
-  q.ldo = g.dim_n;
-  const dim3 grid(en / dev::kXvTile, np / dev::kXvTile);
+  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dz");
+  const int np = xv_npad(g);
+  const dim3 grid(q.En / dev::kXvTile, np / dev::kXvTile);
   dispatch_comp(comp, [&](auto tc) {
     using Tc = decltype(tc);
     // view 1's rows from G, G -> G^T in place, view 2's rows from G^T: both products stream K-major
@@ -751,54 +640,13 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-// ---- distributed form ------------------------------------------------------------------------------
-namespace {
-// The gathered rows [world * rows_pad][ld_k] as the tile kernels read them. A row stage reads 128 rows
-// from local row side * n + I * 128 of the own slot, a column stage from (1 - side) * n + Jl * 128 of
-// slot q: at most local row n + n_pad of a slot, so with n + n_pad <= rows_pad no stage reads beyond
-// its slot, and none beyond the world * rows_pad rows of the buffer.
-dev::XvDistParams xv_dist_params(DType comp, const void* zq_all, const Geometry& g, const char* who) {
-  NTXENT_CHECK(comp == DType::F32 || comp == DType::F16 || comp == DType::BF16,
-               std::string(who) + ": fp32 | fp16 | bf16 rows");
-  NTXENT_CHECK(g.world >= 1 && g.rank >= 0 && g.rank < g.world, std::string(who) + ": bad world / rank");
-  const size_t es = dtype_size(comp), kbytes = (size_t)g.dim_k * es;
-  NTXENT_CHECK(kbytes % kKStepBytes == 0 && g.dim_k <= g.ld_k && kbytes >= kKStepBytes && ((size_t)g.ld_k * es) % 16 == 0,
-               std::string(who) + ": geometry does not pad K to 128 bytes");
-  const int n = g.rows / 2, np = xv_npad(g);
-  NTXENT_CHECK(n + np <= g.rows_pad, std::string(who) + ": a 128-row stage would leave its rank slot");
-  dev::XvDistParams p{};
-  p.zq = static_cast<const char*>(zq_all);
-  p.ldb = (long long)g.ld_k * (long long)es;
-  p.n = n;
-  p.rows_pad = g.rows_pad;
-  p.nk = (int)(kbytes / kKStepBytes);
-  p.nT = np / dev::kXvTile;
-  p.world = g.world;
-  p.rank = g.rank;
-  p.q_skip = -1;
-  p.scale2 = g.inv_temp * dev::kLog2e;
-  return p;
-}
-}  // namespace
-
-size_t xview_dist_part_bytes(const Geometry& g) {
-  return (size_t)g.world * (xv_npad(g) / dev::kXvTile) * g.rows_pad * sizeof(float2);
-}
-size_t xview_dist_lse_scratch_bytes(const Geometry& g) { return (size_t)(g.rows / 2) * sizeof(double); }
-// 4 n_pad W n_pad bytes in every plan (one fp32 plane, or two 16-bit planes): one side at a time
-size_t xview_dist_coef_bytes(DType comp, const Geometry& g) {
-  return (size_t)xv_planes(comp) * xv_npad(g) * g.world * xv_npad(g) * dtype_size(comp);
-}
-size_t xview_dist_zt_bytes(DType comp, const Geometry& g) {
-  return (size_t)2 * xv_en(g) * g.world * xv_npad(g) * dtype_size(comp);
-}
-
+// ---- rank g.rank of g.world ------------------------------------------------------------------------------
 void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, int q_lo, int q_hi, int q_skip,
                            float2* part, float* ypos, hipStream_t stream) {
   NTXENT_CHECK(zq_all && part && ypos, "xview_dist_fwd: null buffer");
   NTXENT_CHECK(0 <= q_lo && q_lo <= q_hi && q_hi <= g.world && q_skip < q_hi && (q_skip < 0 || q_skip >= q_lo),
                "xview_dist_fwd: bad slot range");
-  dev::XvDistParams p = xv_dist_params(comp, zq_all, g, "xview_dist_fwd");
+  dev::XvParams p = xv_params(comp, zq_all, g, "xview_dist_fwd");
   p.q_lo = q_lo;
   p.nq = q_hi - q_lo - (q_skip >= 0 ? 1 : 0);
   p.q_skip = q_skip;
@@ -807,7 +655,7 @@ void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, in
   if (p.nq == 0) return;
   const int ntiles = 2 * p.nT * p.nq * p.nT;
   dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_dist_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+    hipLaunchKernelGGL((dev::xview_fwd_kernel<decltype(tc), false>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
   });
   NTXENT_HIP_CHECK(hipGetLastError());
 }
@@ -815,71 +663,31 @@ void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, in
 void launch_xview_dist_lse(const float2* part, const float* ypos, const Geometry& g, float* lse2_all, float* cpos,
                            double* loss, void* scratch, hipStream_t stream) {
   NTXENT_CHECK(part && ypos && lse2_all && cpos && loss && scratch, "xview_dist_lse: null buffer");
-  const int n = g.rows / 2, nslots = g.world * (xv_npad(g) / dev::kXvTile);
-  double* lpair = static_cast<double*>(scratch);
-  // xview_lse_kernel over this rank's slot of lse2_all: W * nT slots per row instead of nT
-  hipLaunchKernelGGL(dev::xview_lse_kernel, dim3((n + g.rows_pad - g.rows + 255) / 256), dim3(256), 0, stream, part,
-                     ypos, lse2_all + (size_t)g.rank * g.rows_pad, cpos, lpair, n, g.rows_pad, nslots);
-  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpair, n,
-                     (double)g.global_rows, (float*)nullptr, loss);
+  xv_lse_loss(part, ypos, g, lse2_all, cpos, static_cast<double*>(scratch), nullptr, loss, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_dist_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream) {
   NTXENT_CHECK(zq_all && zt, "xview_dist_zt: null buffer");
-  xv_dist_params(comp, zq_all, g, "xview_dist_zt");
-  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
-  dispatch_comp(comp, [&](auto tc) {
-    using Tc = decltype(tc);
-    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2 * g.world), dim3(256), 0, stream,
-                       static_cast<const Tc*>(zq_all), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
-                       (long long)g.world * np, (long long)g.rows_pad, (long long)np);
-  });
+  xv_params(comp, zq_all, g, "xview_dist_zt");
+  xv_launch_zt(comp, zq_all, g, zt, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_dist_coef(DType comp, const void* zq_all, const float* lse2_all, const float* cpos,
                             const Geometry& g, int side, void* coef, hipStream_t stream) {
   NTXENT_CHECK(zq_all && lse2_all && cpos && coef && (side == 0 || side == 1), "xview_dist_coef: bad argument");
-  dev::XvDistParams p = xv_dist_params(comp, zq_all, g, "xview_dist_coef");
-  const int np = xv_npad(g);
-  p.side = side;
-  p.lse2 = lse2_all;
-  p.cpos = cpos;
-  p.gbuf = static_cast<char*>(coef);
-  p.ldg = (long long)g.world * np * (long long)dtype_size(comp);
-  p.plane_bytes = (long long)np * p.ldg;
-  const int ntiles = p.nT * g.world * p.nT;
-  dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_dist_coef_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
-  });
+  xv_launch_coef(comp, xv_params(comp, zq_all, g, "xview_dist_coef"), g, side, lse2_all, cpos, coef, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
                           hipStream_t stream) {
   NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1), "xview_dist_dz: bad argument");
-  xv_dist_params(comp, nullptr, g, "xview_dist_dz");
-  const size_t es = dtype_size(comp);
-  const int np = xv_npad(g), en = xv_en(g);
-  // the dZ tiles write columns [0, En) of rows [side * n, side * n + n) of the [rows_pad][dim_n] slab
-  NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, "xview_dist_dz: dim_n < roundup(dim_k, 128)");
-  // xview_dz_kernel with K = world * n_pad per plane: the planes' rows and Zt's rows both hold the
-  // rank slots side by side, so a plane's K-steps run through the slots in ascending order
-  dev::XvDzParams q{};
-  q.gbuf = static_cast<const char*>(coef);
-  q.ldg = (long long)g.world * np * (long long)es;
-  q.plane_bytes = (long long)np * q.ldg;
-  q.planes = xv_planes(comp);
-  q.zt = static_cast<const char*>(zt);
-  q.ldz = q.ldg;
-  q.En = en;
-  q.n_half = g.rows / 2;
+  xv_params(comp, nullptr, g, "xview_dist_dz");
+  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dist_dz");
   q.side = side;
-  q.nk = (int)((size_t)q.ldg / kKStepBytes);
-  q.out = dz;
-  q.ldo = g.dim_n;
-  const dim3 grid(en / dev::kXvTile, np / dev::kXvTile);
+  const dim3 grid(q.En / dev::kXvTile, xv_npad(g) / dev::kXvTile);
   dispatch_comp(comp, [&](auto tc) {
     hipLaunchKernelGGL((dev::xview_dz_kernel<decltype(tc)>), grid, dim3(dev::kXvThreads), 0, stream, q);
   });

@@ -315,6 +315,35 @@ std::vector<at::Tensor> xview_forward(const at::Tensor& h, double T, const std::
   return {loss, st[1], lse2, cpos};
 }
 
+// The forward's statistics: lse2_all [world * rows_pad] (one GPU: world 1) and cpos [rows_pad], and
+// what a backward takes besides, inv [rows]. msg: a caller's own message for all of them.
+static void check_xview_stats(const at::Tensor& lse2_all, const at::Tensor& cpos, const Geometry& g,
+                              const char* msg = nullptr) {
+  NTXENT_CHECK(lse2_all.numel() == (long)g.world * g.rows_pad && lse2_all.scalar_type() == at::kFloat,
+               msg ? msg : "lse2_all must be float32 [world*rows_pad]");
+  NTXENT_CHECK(cpos.numel() == g.rows_pad && cpos.scalar_type() == at::kFloat,
+               msg ? msg : "cpos must be float32 [rows_pad]");
+}
+static void check_xview_saved(const at::Tensor& inv, const at::Tensor& lse2_all, const at::Tensor& cpos,
+                              const Geometry& g, const char* msg) {
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, msg);
+  check_xview_stats(lse2_all, cpos, g, msg);
+}
+
+// The end of both backwards: coef and zt are released before dh exists, then the grad_out / (2N tau)
+// scaling and the normalisation backward of the slab; dot: also dot_i = z_i . (C z)_i, [rows].
+static at::Tensor xview_backward_tail(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& go,
+                                      const at::Tensor& dz, at::Tensor& coef, at::Tensor& zt, const Geometry& g,
+                                      hipStream_t stream, at::Tensor* dot = nullptr) {
+  coef.reset();
+  zt.reset();
+  auto dh = at::empty_like(h);
+  if (dot) *dot = at::empty({g.rows}, opts(h, at::kFloat));
+  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
+                  go.data_ptr<float>(), dh.data_ptr(), g, stream, nullptr, 0, dot ? dot->data_ptr<float>() : nullptr);
+  return dh;
+}
+
 // want_tau: also dL/dtau times grad_out, a 0-d fp32 tensor; undefined otherwise. compute: the
 // forward's.
 static std::pair<at::Tensor, at::Tensor> xview_backward_impl(const at::Tensor& h, const at::Tensor& inv,
@@ -326,10 +355,8 @@ static std::pair<at::Tensor, at::Tensor> xview_backward_impl(const at::Tensor& h
   const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
   auto P = xview_plan(h, T, comp);
   const Geometry& g = P->g;
-  NTXENT_CHECK(inv.numel() == g.rows && lse2.numel() == g.rows_pad && cpos.numel() == g.rows_pad &&
-                   inv.scalar_type() == at::kFloat && lse2.scalar_type() == at::kFloat &&
-                   cpos.scalar_type() == at::kFloat,
-               "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
+  check_xview_saved(inv, lse2, cpos, g,
+                    "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
   const hipStream_t stream = cur_stream(h);
   auto go = grad_scalar(grad_out);
   // buffers live only as long as a stage needs them (stream-ordered reuse by the allocator): the
@@ -350,14 +377,8 @@ static std::pair<at::Tensor, at::Tensor> xview_backward_impl(const at::Tensor& h
   }
   auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
   launch_xview_dz(comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
-  coef.reset();
-  zt.reset();
-  auto dh = at::empty_like(h);
-  auto dot = at::empty({g.rows}, opts(h, at::kFloat));
-  // grad_out / (R tau) scaling, the normalisation backward and dot_i = z_i . (C z)_i
-  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
-                  go.data_ptr<float>(), dh.data_ptr(), g, stream, nullptr, 0, dot.data_ptr<float>());
-  at::Tensor dtau;
+  at::Tensor dot, dtau;
+  auto dh = xview_backward_tail(h, inv, go, dz, coef, zt, g, stream, &dot);
   if (want_tau) {
     dtau = at::empty({}, opts(h, at::kFloat));
     launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau.data_ptr<float>(), g, stream);
@@ -393,14 +414,18 @@ static void check_xview_dist(const at::Tensor& zq_all, const Plan& P) {
 // Forward tiles of both sides against the rank slots [q_lo, q_hi) except q_skip (-1: none) into
 // part (float32 [xview_dist_part_slots, rows_pad, 2]) and ypos (float32 [>= rows / 2]). The own slot
 // (q == rank) needs only this rank's rows, so its tiles can run while the others are gathered.
+static void check_xview_part(const at::Tensor& part, const at::Tensor& ypos, const Plan& P) {
+  check_input(part, "part");
+  check_input(ypos, "ypos");
+  NTXENT_CHECK(part.numel() * 4 == (long)xview_part_bytes(P.g) && part.scalar_type() == at::kFloat,
+               "part must be float32 [world * n_pad / 128, rows_pad, 2]");
+  NTXENT_CHECK(ypos.numel() >= P.g.rows / 2 && ypos.scalar_type() == at::kFloat, "ypos must be float32 [>= rows / 2]");
+}
+
 void xview_dist_fwd(const at::Tensor& zq_all, const Plan& P, at::Tensor& part, at::Tensor& ypos, int q_lo, int q_hi,
                     int q_skip) {
   check_xview_dist(zq_all, P);
-  check_input(part, "part");
-  check_input(ypos, "ypos");
-  NTXENT_CHECK(part.numel() * 4 == (long)xview_dist_part_bytes(P.g) && part.scalar_type() == at::kFloat,
-               "part must be float32 [world * n_pad / 128, rows_pad, 2]");
-  NTXENT_CHECK(ypos.numel() >= P.g.rows / 2 && ypos.scalar_type() == at::kFloat, "ypos must be float32 [>= rows / 2]");
+  check_xview_part(part, ypos, P);
   const at::DeviceGuard guard(zq_all.device());
   launch_xview_dist_fwd(P.comp, zq_all.data_ptr(), P.g, q_lo, q_hi, q_skip,
                         reinterpret_cast<float2*>(part.data_ptr<float>()), ypos.data_ptr<float>(), cur_stream(zq_all));
@@ -411,15 +436,10 @@ void xview_dist_fwd(const at::Tensor& zq_all, const Plan& P, at::Tensor& part, a
 // rounded to float32 once, gives the loss).
 at::Tensor xview_dist_lse(const at::Tensor& part, const at::Tensor& ypos, at::Tensor& lse2_all, at::Tensor& cpos,
                           const Plan& P) {
-  check_input(part, "part");
-  NTXENT_CHECK(part.numel() * 4 == (long)xview_dist_part_bytes(P.g) && part.scalar_type() == at::kFloat,
-               "part must be float32 [world * n_pad / 128, rows_pad, 2]");
-  NTXENT_CHECK(ypos.numel() >= P.g.rows / 2 && ypos.scalar_type() == at::kFloat, "ypos must be float32 [>= rows / 2]");
-  NTXENT_CHECK(lse2_all.numel() == (long)P.g.world * P.g.rows_pad && lse2_all.scalar_type() == at::kFloat,
-               "lse2_all must be float32 [world*rows_pad]");
-  NTXENT_CHECK(cpos.numel() == P.g.rows_pad && cpos.scalar_type() == at::kFloat, "cpos must be float32 [rows_pad]");
+  check_xview_part(part, ypos, P);
+  check_xview_stats(lse2_all, cpos, P.g);
   const at::DeviceGuard guard(part.device());
-  auto scratch = at::empty({(long)(xview_dist_lse_scratch_bytes(P.g) / 8)}, opts(part, at::kDouble));
+  auto scratch = at::empty({(long)(xview_lse_scratch_bytes(P.g) / 8)}, opts(part, at::kDouble));
   auto loss = at::empty({}, opts(part, at::kDouble));
   launch_xview_dist_lse(reinterpret_cast<const float2*>(part.data_ptr<float>()), ypos.data_ptr<float>(), P.g,
                         lse2_all.data_ptr<float>(), cpos.data_ptr<float>(), loss.data_ptr<double>(), scratch.data_ptr(),
@@ -437,15 +457,13 @@ at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, co
   check_xview_dist(zq_all, P);
   const Geometry& g = P.g;
   NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  NTXENT_CHECK(inv.numel() == g.rows && cpos.numel() == g.rows_pad && lse2_all.numel() == (long)g.world * g.rows_pad &&
-                   inv.scalar_type() == at::kFloat && cpos.scalar_type() == at::kFloat &&
-                   lse2_all.scalar_type() == at::kFloat,
-               "xview_dist_backward: inv [rows], cpos [rows_pad], lse2_all [world*rows_pad] in float32");
+  check_xview_saved(inv, lse2_all, cpos, g,
+                    "xview_dist_backward: inv [rows], cpos [rows_pad], lse2_all [world*rows_pad] in float32");
   const at::DeviceGuard guard(h.device());
   const hipStream_t stream = cur_stream(h);
   auto go = grad_scalar(grad_out);
-  auto zt = at::empty({(long)xview_dist_zt_bytes(P.comp, g)}, opts(h, at::kByte));
-  auto coef = at::empty({(long)xview_dist_coef_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto coef = at::empty({(long)xview_coef_bytes(P.comp, g)}, opts(h, at::kByte));
   auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
   launch_xview_dist_zt(P.comp, zq_all.data_ptr(), g, zt.data_ptr(), stream);
   for (int side = 0; side < 2; ++side) {
@@ -453,12 +471,7 @@ at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, co
                            coef.data_ptr(), stream);
     launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), stream);
   }
-  coef.reset();
-  zt.reset();
-  auto dh = at::empty_like(h);
-  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
-                  go.data_ptr<float>(), dh.data_ptr(), g, stream);
-  return dh;
+  return xview_backward_tail(h, inv, go, dz, coef, zt, g, stream);
 }
 
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {
@@ -1476,8 +1489,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xview_forward", &xview_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto");
   m.def("xview_backward", &xview_backward);
   m.def("xview_backward_tau", &xview_backward_tau);
-  m.def("xview_dist_part_slots", [](const Plan& P) { return (long)(xview_dist_part_bytes(P.g) / 8 / P.g.rows_pad); });
-  m.def("xview_dist_coef_bytes", [](const Plan& P) { return (long)xview_dist_coef_bytes(P.bwd(), P.g); });
+  m.def("xview_dist_part_slots", [](const Plan& P) { return (long)(xview_part_bytes(P.g) / 8 / P.g.rows_pad); });
+  m.def("xview_dist_coef_bytes", [](const Plan& P) { return (long)xview_coef_bytes(P.bwd(), P.g); });
   m.def("xview_dist_fwd", &xview_dist_fwd, py::arg("zq_all"), py::arg("plan"), py::arg("part"), py::arg("ypos"),
         py::arg("q_lo"), py::arg("q_hi"), py::arg("q_skip") = -1);
   m.def("xview_dist_lse", &xview_dist_lse, py::arg("part"), py::arg("ypos"), py::arg("lse2_all"), py::arg("cpos"),

@@ -83,7 +83,10 @@ def _emulate(shards, compute, temperature=T):
 
 # ---- 1. emulated parity with the fp64 oracle on the global batch ----------------------------------------
 CASES = [(2, 37, 40, "fp32"), (3, 129, 160, "fp32"), (3, 129, 160, "fp16"), (2, 200, 100, "bf16"),
-         (4, 128, 64, "fp32"), (8, 37, 40, "fp16")]
+         (4, 128, 64, "fp32"), (8, 37, 40, "fp16"),
+         # world 1: the stage ops as the one-GPU op rides on them (a second tile of one valid row,
+         # three fp16 K-steps)
+         (1, 129, 160, "fp16"), (1, 37, 40, "fp32")]
 
 
 @functools.lru_cache(maxsize=None)
