@@ -1446,6 +1446,11 @@ bool launch_fwd_stats(DType comp, const void* zq_local, const void* zq_all, cons
                "diagonal remainder: workspace too small");
   const int nmain = ntiles - nstrip;
   const int pieces = part_x == nullptr ? fwd_splitk_pieces(ntiles, nk_tile, cus, diag_tail) : 0;
+  // diag_up_kernel and sk_reduce_kernel apply the pair rule (pair_mask.h) without a test of the tile
+  // kind: both get own-block tiles only. The remainder lies inside the diagonal tail, and split-K
+  // runs own-block launches (a diagonal tail, no cross partials) only.
+  NTXENT_CHECK(nstrip <= diag_tail && (pieces == 0 || (diag_tail > 0 && part_x == nullptr)),
+               "fwd_stats: diagonal remainder / split-K forward outside the own block");
   int grid;
   if (pieces > 0) {
     // split-K: tile-aligned pieces, piece-major over the blocks (the XCD-contiguous block runs

@@ -23,6 +23,7 @@
 //   pos_rank_finish : hard_neg_cos back from its integer image to fp32, in place.
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
+#include "pair_mask.h"
 #include "host_common.h"
 #include "tile128.h"
 
@@ -151,14 +152,13 @@ __global__ __launch_bounds__(kTile128Threads) void pos_rank_kernel(const RankPar
     for (int r = 0; r < 4; ++r) {
       const int rt = 64 * wr + 16 * mi + 4 * g + r;
       const int gi = I * kRankTile + rt;
-      const int gp = gi < p.n_half ? gi + p.n_half : gi - p.n_half;
       const float ti = s_t[rt];
       float m = kNegInf;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const float v = acc[mi][ni][r];
-        // self, the positive and everything at or beyond R (pad rows have cosine 0) are no negatives
-        const bool ok = (gi < p.R) & (gj[ni] < p.R) & (gj[ni] != gi) & (gj[ni] != gp);
+        // (pad rows have cosine 0, and are no negatives)
+        const bool ok = pair::is_negative(gi, gj[ni], p.R, p.n_half);
         cnt_r[mi] += (int)(ok & (v > ti)) << (8 * r);
         cnt_c += (int)(ok & (v > tc[ni])) << (8 * ni);
         const float vm = ok ? v : kNegInf;

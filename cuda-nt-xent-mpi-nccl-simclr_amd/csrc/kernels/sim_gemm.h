@@ -28,6 +28,7 @@
 
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
+#include "pair_mask.h"
 
 #include <type_traits>
 
@@ -222,6 +223,26 @@ __device__ __forceinline__ long long ctile_index(const SimParams& p, int mt, int
   return (long long)mt * p.c_ld + cs;
 }
 
+// One coefficient element, shared by coef_epilogue and coef_epilogue_q8 (the pair rule itself is
+// pair_mask.h's; columns are global indices of the gathered range, the own block starts at own0).
+// Value of a negative, y in log2 units. Fixed-shift form (2M < 120, see the forward epilogue):
+// C = 2^(y - M) * (2^(M - lse2_i) + 2^(M - lse2_j)), one exp2 per element, lrow / lcol holding the
+// two powers; else lrow / lcol are the LSEs themselves.
+__device__ __forceinline__ float coef_value(bool fixed, float y, float M, float lrow, float lcol) {
+  return fixed ? fast_exp2(y - M) * (lrow + lcol) : fast_exp2(y - lrow) + fast_exp2(y - lcol);
+}
+// Column preamble: tile column col_t of column tile nt -> global column, its LSE term and validity.
+__device__ __forceinline__ void coef_col(const SimParams& p, int nt, int col_local0, int col_t, int& gj, float& lcol,
+                                         bool& cvalid) {
+  gj = nt * kTile + col_t;
+  const float l = p.lse2[gj];
+  lcol = p.fixed_shift != 0 ? fast_exp2(p.y_scale - l) : l;
+  cvalid = (col_local0 + col_t) < p.R;
+}
+// (Self, positive and validity of an element: row gi's self column is own0 + gi, its positive
+// own0 + pair::partner(gi); both epilogues test them in place. As member functions of a row
+// object the same tests compiled to different code in the coefficient GEMM.)
+
 // ------------------------------------------------------------------------------------
 // Coefficient epilogue shared by the store-mode coef kernel (NW = 1: one wave, a 128x64
 // region at (row_base, col_base)) and the recompute GEMM (NW = 8: the whole tile).
@@ -248,21 +269,13 @@ __device__ __forceinline__ void coef_epilogue(f32x4 (&acc)[NMI][4], const int (&
   constexpr int NT = NW * 64;        // threads in the calling block
   T* base = reinterpret_cast<T*>(p.cbuf);
   const int col_local0 = (nt * kTile) % p.Rpad;  // rank-local column of this tile's col 0
-  // Fixed-shift form (2M < 120, see the forward epilogue):
-  // C = 2^(y - M) * (2^(M - lse2_i) + 2^(M - lse2_j)), one exp2 per element.
   const bool fixed = p.fixed_shift != 0;
   const float M = p.y_scale;
   float lcol[4];
   bool cvalid[4];
   int gj[4];
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int col_t = cb[ni] + (lane & 15);
-    gj[ni] = nt * kTile + col_t;
-    const float l = p.lse2[gj[ni]];
-    lcol[ni] = fixed ? fast_exp2(M - l) : l;
-    cvalid[ni] = (col_local0 + col_t) < p.R;
-  }
+  for (int ni = 0; ni < 4; ++ni) coef_col(p, nt, col_local0, cb[ni] + (lane & 15), gj[ni], lcol[ni], cvalid[ni]);
   T* slot = base + ctile_index(p, mt, nt) * kTileElems;
   T* mirror = nullptr;
   // (kTileDiagUp: the same tile's slot; half C: no lower off-diagonal tiles, the dZ reads C_JI^T)
@@ -278,14 +291,11 @@ __device__ __forceinline__ void coef_epilogue(f32x4 (&acc)[NMI][4], const int (&
   // slot-major ([slot][Rpad]: a store instruction's lanes hold neighbouring rows)
   const int wq = NW == 8 ? ((threadIdx.x >> 6) & 3) : (col_base >> 6);  // column quarter of this wave
   float cdot[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  // plain region (uniform): no self or positive element and no padding among this call's rows x
-  // columns, so C is the exponential alone, without the per-element compares and selects
+  // plain region (uniform; pair::window_plain): C is the exponential alone, without the
+  // per-element compares and selects
   // (coefficient pass -10 % at the headline and config 2: profiles/r4/variants_r4_v25_coefplain.md)
-  const int r_lo = mt * kTile + row_base, r_hi = r_lo + NROWS;
-  const int c_lo = nt * kTile + col_base, c_hi = c_lo + NCOLS;
-  auto hits = [&](int a0) { return a0 < c_hi && c_lo < a0 + NROWS; };
-  const bool plain = fixed && r_hi <= p.R && col_local0 + col_base + NCOLS <= p.R && !hits(p.own0 + r_lo) &&
-                     !hits(p.own0 + r_lo + p.n_half) && !hits(p.own0 + r_lo - p.n_half);
+  const bool plain = fixed && pair::window_plain(mt * kTile + row_base, NROWS, nt * kTile + col_base, NCOLS, p.own0, p.R,
+                                                 p.n_half, col_local0 + col_base);
   // (row LSEs of all blocks loaded up front and the dot partials stored after the block loop,
   // one transposing reduction per 4 rows: the pass measured 42 -> 44 us at the headline and
   // 149 -> 154 us at config 5, not kept; the e4m3 epilogue below gains from the same change)
@@ -301,7 +311,7 @@ __device__ __forceinline__ void coef_epilogue(f32x4 (&acc)[NMI][4], const int (&
       for (int r = 0; r < 4; ++r) {
         const float lrow = fast_exp2(M - lrow4[r]);
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) c[ni][r] = fast_exp2(acc[mi][ni][r] * p.acc_scale - M) * (lrow + lcol[ni]);
+        for (int ni = 0; ni < 4; ++ni) c[ni][r] = coef_value(true, acc[mi][ni][r] * p.acc_scale, M, lrow, lcol[ni]);
       }
     } else
 #pragma unroll
@@ -309,12 +319,10 @@ __device__ __forceinline__ void coef_epilogue(f32x4 (&acc)[NMI][4], const int (&
       const int gi = gi0 + r;
       const bool rvalid = gi < p.R;
       const float lrow = fixed ? fast_exp2(M - lrow4[r]) : lrow4[r];
-      const int gself = p.own0 + gi;
-      const int gpos = p.own0 + (gi < p.n_half ? gi + p.n_half : gi - p.n_half);
+      const int gself = p.own0 + gi, gpos = p.own0 + pair::partner(gi, p.n_half);  // global columns
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
-        const float y = acc[mi][ni][r] * p.acc_scale;
-        float v = fixed ? fast_exp2(y - M) * (lrow + lcol[ni]) : fast_exp2(y - lrow) + fast_exp2(y - lcol[ni]);
+        float v = coef_value(fixed, acc[mi][ni][r] * p.acc_scale, M, lrow, lcol[ni]);
         v = (gj[ni] == gpos) ? cpos4[r] : v;  // positive: -(a_i + a_p), no 1 - P cancellation
         v = (rvalid && cvalid[ni] && gj[ni] != gself) ? v : 0.0f;
         c[ni][r] = v;
@@ -478,22 +486,15 @@ __device__ __forceinline__ void coef_epilogue_q8(f32x4 (&acc)[4][4], const int (
   int gj[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
-    const int col_t = cb[ni] + (lane & 15);
-    gj[ni] = nt * kTile + col_t;
-    const float l = p.lse2[gj[ni]];
-    lcol[ni] = fixed ? fast_exp2(M - l) : l;
-    cvalid[ni] = (col_local0 + col_t) < p.R;
+    coef_col(p, nt, col_local0, cb[ni] + (lane & 15), gj[ni], lcol[ni], cvalid[ni]);
     const int e = q8_row_exp(p.q8_mneg[gj[ni]], lmin);
     scol[ni] = exp2i(e);
     icol[ni] = exp2i(-e);
   }
   float dsv[4];  // row partial of row (lane >> 2) & 3 of each 4-row block (stored after the loop)
   // plain region: as coef_epilogue
-  const int r_lo = mt * kTile + row_base, r_hi = r_lo + 64;
-  const int c_lo = nt * kTile + col_base, c_hi = c_lo + 64;
-  auto hits = [&](int a0) { return a0 < c_hi && c_lo < a0 + 64; };
-  const bool plain = fixed && r_hi <= p.R && col_local0 + col_base + 64 <= p.R && !hits(p.own0 + r_lo) &&
-                     !hits(p.own0 + r_lo + p.n_half) && !hits(p.own0 + r_lo - p.n_half);
+  const bool plain = fixed && pair::window_plain(mt * kTile + row_base, 64, nt * kTile + col_base, 64, p.own0, p.R,
+                                                 p.n_half, col_local0 + col_base);
   const int wq = col_base >> 6;
   float cdot[4] = {0.f, 0.f, 0.f, 0.f}, cposd[4] = {0.f, 0.f, 0.f, 0.f};
   // quad byte transpose (lane q of a quad holds bytes M[q][0..3]; afterwards T[q][r] = M[r][q]):
@@ -525,16 +526,14 @@ __device__ __forceinline__ void coef_epilogue_q8(f32x4 (&acc)[4][4], const int (
       float c[4];
       if (plain) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) c[r] = fast_exp2(acc[mi][ni][r] * p.acc_scale - M) * (lrow[r] + lcol[ni]);
+        for (int r = 0; r < 4; ++r) c[r] = coef_value(true, acc[mi][ni][r] * p.acc_scale, M, lrow[r], lcol[ni]);
       } else {
         const f32x4 cpos4 = *reinterpret_cast<const f32x4*>(p.cpos + gi0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int gi = gi0 + r;
-          const int gself = p.own0 + gi;
-          const int gpos = p.own0 + (gi < p.n_half ? gi + p.n_half : gi - p.n_half);
-          const float y = acc[mi][ni][r] * p.acc_scale;
-          const float v = fixed ? fast_exp2(y - M) * (lrow[r] + lcol[ni]) : fast_exp2(y - lrow[r]) + fast_exp2(y - lcol[ni]);
+          const int gself = p.own0 + gi, gpos = p.own0 + pair::partner(gi, p.n_half);  // global columns
+          const float v = coef_value(fixed, acc[mi][ni][r] * p.acc_scale, M, lrow[r], lcol[ni]);
           const bool ok = gi < p.R && cvalid[ni] && gj[ni] != gself;
           const bool pos = ok && gj[ni] == gpos;
           c[r] = (ok && !pos) ? v : 0.0f;
@@ -747,7 +746,7 @@ __device__ __forceinline__ void dz8_finish(f32x4 (&acc)[8][4], const SimParams& 
     const bool mv = m < p.R;
     const float f = exp2i(-q8_row_exp(p.q8_mneg[m], lmin) - 8);
     const float cp = mv ? p.cpos[m] : 0.f;
-    const int pm = mv ? (m < p.n_half ? m + p.n_half : m - p.n_half) : 0;
+    const int pm = mv ? NTXENT_PAIR_PARTNER(m, p.n_half) : 0;  // (= pair::partner: see pair_mask.h)
     const _Float16* zp = p.q8_zq + (long long)pm * p.q8_ldz;
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
@@ -1696,20 +1695,16 @@ __global__ __launch_bounds__(kGemmThreads) void sim_gemm_kernel(const SimParams 
     const bool col_out = kind == kTileSymOff || kind == kTileCross;  // column partials too
     constexpr bool fixed = FX != 0;  // launch_sim_gemm picks FX = p.fixed_shift
     const float M = p.y_scale;
-    // Masks set the masked raw values of a 16-row block to -inf (exp2 -> 0). Element (tile row
-    // tr, tile col tc) is the self pair when tc - tr == r0 - c0 and a positive when tc - tr ==
-    // r0 - c0 +- n_half; a 16x16 fragment can hold such an element only if its block offset
-    // cb - rb is within 15 of that difference, and padding only at the tile edge. These tests
-    // are wave-uniform, so only the few fragments that need it run per-lane selects; the
+    // Masks set the masked raw values of a 16-row block to -inf (exp2 -> 0): the pair rule and
+    // its conservative wave-uniform pre-tests are pair::TileMask's (pair_mask.h); padding lies
+    // only at the tile edge. Only the few fragments that need it run per-lane selects; the
     // per-element masked form compiled to per-element control flow (~15 us per tile) and the
     // fully unrolled select form spilled the main loop.
     const int r0 = mt * kTile, c0 = col_local0;
-    const int D0 = r0 - c0, D1 = D0 + p.n_half, D2 = D0 - p.n_half;
+    const pair::TileMask tm(p.R, p.n_half, r0, c0);
+    const int D0 = tm.D0, D1 = tm.D1, D2 = tm.D2;
     const bool pad = (r0 + kTile > p.R) || (c0 + kTile > p.R);
-    // fragment offsets cb - rb span [-240, 240]: only tiles with some |D| <= 255 hold a self
-    // or positive element (the diagonal band and the two positive bands of the own block)
-    const bool tile_near = own_blk && ((D0 <= 255 && D0 >= -255) || (D1 <= 255 && D1 >= -255) ||
-                                       (D2 <= 255 && D2 >= -255));
+    const bool tile_near = own_blk && tm.near();
     const bool mask_any = tile_near || pad;
     // block offsets from the wave index in an SGPR: the tests compile to scalar branches
     const int ws = __builtin_amdgcn_readfirstlane(w);
@@ -1720,6 +1715,7 @@ __global__ __launch_bounds__(kGemmThreads) void sim_gemm_kernel(const SimParams 
         const int rbs = 128 * (mi >> 2) + 64 * was + 16 * (mi & 3);
         const int cbs = 128 * (ni >> 1) + 32 * wbs + 16 * (ni & 1);
         const int off = cbs - rbs;
+        // (= tm.fragment_near(off), written out like the per-element line below)
         const bool near = tile_near && ((off - D0 <= 15 && D0 - off <= 15) || (off - D1 <= 15 && D1 - off <= 15) ||
                                         (off - D2 <= 15 && D2 - off <= 15));
         const bool edge = (r0 + rbs + 16 > p.R) || (c0 + cbs + 16 > p.R);
@@ -1729,6 +1725,8 @@ __global__ __launch_bounds__(kGemmThreads) void sim_gemm_kernel(const SimParams 
           for (int r = 0; r < 4; ++r) {
             const int tr = rb[mi] + 4 * (lane >> 4) + r;
             const int gi = r0 + tr, d = tc - tr;
+            // = tm.drop(tr, tc, tile_near), kept written out: through the helpers the forward
+            // instantiations compile to different code (this kernel sits at its register limit)
             const bool drop = (gi >= p.R) | (c0 + tc >= p.R) |
                               (tile_near & ((d == D0) | ((d == D1) & (gi < p.n_half)) | ((d == D2) & (gi >= p.n_half))));
             acc[mi][ni][r] = drop ? kNegInf : acc[mi][ni][r];
@@ -1926,6 +1924,72 @@ __global__ __launch_bounds__(64) void coef_kernel(const SimParams p) {
     coef_epilogue_q8<T>(acc, rb, cb, 128 * wm + 64 * half, 64 * wn, t.x, t.y, kind, (lds_char*)smem, p, lane);
   else
     coef_epilogue<T, 1, 4>(acc, rb, cb, 128 * wm + 64 * half, 64 * wn, t.x, t.y, kind, (lds_char*)smem, p, lane);
+}
+
+// ------------------------------------------------------------------------------------
+// The 64-column forward epilogue of one wave, shared by the diagonal remainder (diag_up_region)
+// and the split-K reduce (sk_reduce_kernel). v[f][r] holds the cosine of tile row
+// row0 + 4 (lane >> 4) + r and tile column col0 + 16 f + (lane & 15) of an OWN-BLOCK tile (tm).
+//   st != nullptr: the kept cosines go to the tile's slot st in canonical fragment order (16-byte
+//                  units of two fragments through sc_unit, fp32 per fragment), before the masks;
+//   v becomes the masked logits in log2 units (tm.drop -> -inf, else v * sc_);
+//   row_out(r, m, s): the (max, sum) partial of row r over the 64 columns (every lane of the
+//                  DPP row holds it), handed over as soon as it is formed;
+// fwd64_cols, for the callers that want column partials, runs on the masked v afterwards:
+//   col_out(f, m, s): likewise for column f over the wave's 16 rows (every lane). It is a
+//                  function of its own so that it sits inside the caller's branch, next to what
+//                  the caller does with the partials (as one function with a flag, and with the
+//                  partials returned in arrays, diag_up_kernel spilled more SGPRs).
+// FX: fixed shift M (one exponential per element and partial; an empty partial reports -inf);
+// else the partial's own maximum.
+// ------------------------------------------------------------------------------------
+template <typename TS, int FX, typename ROW_OUT>
+__device__ __forceinline__ void fwd64_epilogue(f32x4 (&v)[4], const pair::TileMask& tm, int row0, int col0, int lane,
+                                               TS* st, float sc_, float M, ROW_OUT&& row_out) {
+  if (st) {
+    if constexpr (sizeof(TS) == 2) {
+#pragma unroll
+      for (int np = 0; np < 2; ++np) {
+        union { TS h[8]; u32x4 u; } pk;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          pk.h[r] = from_f32<TS>(v[2 * np][r]);
+          pk.h[4 + r] = from_f32<TS>(v[2 * np + 1][r]);
+        }
+        *reinterpret_cast<u32x4*>(st + sc_unit(row0, col0 + 32 * np, lane) * 8) = pk.u;
+      }
+    } else {
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+        *reinterpret_cast<f32x4*>(st + (((row0 >> 4) * 16 + ((col0 + 16 * f) >> 4)) * 64 + lane) * 4) = v[f];
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      v[f][r] = tm.drop(row0 + 4 * (lane >> 4) + r, col0 + 16 * f + (lane & 15)) ? kNegInf : v[f][r] * sc_;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float m = M;
+    if constexpr (!FX) m = row16_max(fmaxf(fmaxf(v[0][r], v[1][r]), fmaxf(v[2][r], v[3][r])));
+    const float ms = (m == kNegInf) ? 0.f : m;
+    float s = (fast_exp2(v[0][r] - ms) + fast_exp2(v[1][r] - ms)) + (fast_exp2(v[2][r] - ms) + fast_exp2(v[3][r] - ms));
+    s = row16_sum(s);
+    row_out(r, FX ? (s > 0.f ? M : kNegInf) : m, s);
+  }
+}
+template <int FX, typename COL_OUT>
+__device__ __forceinline__ void fwd64_cols(const f32x4 (&v)[4], float M, COL_OUT&& col_out) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    float m = M;
+    if constexpr (!FX) m = xrow_max(fmaxf(fmaxf(v[f][0], v[f][1]), fmaxf(v[f][2], v[f][3])));
+    const float ms = (m == kNegInf) ? 0.f : m;
+    float s = (fast_exp2(v[f][0] - ms) + fast_exp2(v[f][1] - ms)) + (fast_exp2(v[f][2] - ms) + fast_exp2(v[f][3] - ms));
+    s = xrow_sum(s);
+    col_out(f, FX ? (s > 0.f ? M : kNegInf) : m, s);
+  }
 }
 
 // Ring of the diagonal-remainder kernel below: a stage holds 64 A + 64 B rows of one K-step.
@@ -2221,72 +2285,30 @@ __device__ __forceinline__ void diag_up_region(const SimParams& p, float2* __res
     for (int f = 0; f < 4; ++f) acc[f] = sum[f];
   }
   dmark(3);
-  // lane holds S[row 64a + 16w + 4 (lane >> 4) + r][col 64b + 16 f + (lane & 15)] (tile-local)
-  const int rb0 = 64 * a + 16 * w;
-  if (p.sc) {  // kept cosines of region (a, b), canonical fragment order, before the masks
-    TS* sto = reinterpret_cast<TS*>(p.sc) + (long long)tile * kTileElems;
-    if constexpr (sizeof(TS) == 2) {
-#pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2) {
-        union { TS h[8]; u32x4 u; } pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          pk.h[r] = from_f32<TS>(acc[2 * h2][r]);
-          pk.h[4 + r] = from_f32<TS>(acc[2 * h2 + 1][r]);
-        }
-        *reinterpret_cast<u32x4*>(sto + sc_unit(rb0, 64 * b + 32 * h2, lane) * 8) = pk.u;
-      }
-    } else {
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-        *reinterpret_cast<f32x4*>(sto + (((rb0 >> 4) * 16 + ((64 * b + 16 * f) >> 4)) * 64 + lane) * 4) = acc[f];
-    }
-  }
-  const int r0 = mt * kTile, c0 = (nt * kTile) % p.Rpad;
-  const int D0 = r0 - c0, D1 = D0 + p.n_half, D2 = D0 - p.n_half;
-  const float sc_ = p.acc_scale, M = p.y_scale;
-  // masked logits (log2 units)
-  float y[4][4];  // [r][f]
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int tr = rb0 + 4 * (lane >> 4) + r, gi = r0 + tr;
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      const int tc = 64 * b + 16 * f + (lane & 15), d = tc - tr;
-      const bool drop = (gi >= p.R) | (c0 + tc >= p.R) | (d == D0) | ((d == D1) & (gi < p.n_half)) |
-                        ((d == D2) & (gi >= p.n_half));
-      y[r][f] = drop ? kNegInf : acc[f][r] * sc_;
-    }
-  }
+  // this wave's 16 rows x 64 columns of region (a, b): kept cosines, masks and partials by
+  // fwd64_epilogue. The remainder's tiles are diagonal tiles of the own block (launch_fwd_stats:
+  // the last diag_tail entries of an own-block list), so the pair rule applies without a test of
+  // the tile kind.
+  const int r0 = mt * kTile;
+  const pair::TileMask tm(p.R, p.n_half, r0, (nt * kTile) % p.Rpad);
+  TS* const sto = p.sc ? reinterpret_cast<TS*>(p.sc) + (long long)tile * kTileElems : nullptr;
   // row partials of group a over b's 64 columns -> contribution (a, slot b)
-  const auto rrs = __builtin_amdgcn_make_buffer_rsrc(scratch + (size_t)(tile * 4 + a) * 4 * 64, 0, 4 * 64 * 8, 0x00020000);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float m = M;
-    if constexpr (!FX) m = row16_max(fmaxf(fmaxf(y[r][0], y[r][1]), fmaxf(y[r][2], y[r][3])));
-    const float ms = (m == kNegInf) ? 0.f : m;
-    float sr = (fast_exp2(y[r][0] - ms) + fast_exp2(y[r][1] - ms)) + (fast_exp2(y[r][2] - ms) + fast_exp2(y[r][3] - ms));
-    sr = row16_sum(sr);
-    const float mo = FX ? (sr > 0.f ? M : kNegInf) : m;
-    if ((lane & 15) == 0)  // write-through: merged by the row group's last contributor on any XCD
-      __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(mo), __float_as_uint(sr)}, rrs,
-                                            (b * 64 + 16 * w + 4 * (lane >> 4) + r) * 8, 0, 16);
-  }
   // column partials of group b over a's 64 rows (off-diagonal regions) -> contribution (b, slot a):
   // per wave over its 16 rows, then the 4 waves merged in wave order through LDS
+  fwd64_epilogue<TS, FX>(
+      acc, tm, 64 * a + 16 * w, 64 * b, lane, sto, p.acc_scale, p.y_scale,
+      [&](int r, float m, float sr) {
+        const auto rrs = __builtin_amdgcn_make_buffer_rsrc(scratch + (size_t)(tile * 4 + a) * 4 * 64, 0, 4 * 64 * 8, 0x00020000);
+        if ((lane & 15) == 0)  // write-through: merged by the row group's last contributor on any XCD
+          __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(m), __float_as_uint(sr)}, rrs,
+                                                (b * 64 + 16 * w + 4 * (lane >> 4) + r) * 8, 0, 16);
+      });
   if (!dg) {
     typedef __attribute__((address_space(3))) f32x2 lds_f2;
     lds_f2* xw = (lds_f2*)(lds + kSubStages * kSubStage);  // [4 waves][64 cols]
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      float m = M;
-      if constexpr (!FX) m = xrow_max(fmaxf(fmaxf(y[0][f], y[1][f]), fmaxf(y[2][f], y[3][f])));
-      const float ms = (m == kNegInf) ? 0.f : m;
-      float sc = (fast_exp2(y[0][f] - ms) + fast_exp2(y[1][f] - ms)) + (fast_exp2(y[2][f] - ms) + fast_exp2(y[3][f] - ms));
-      sc = xrow_sum(sc);
-      const float mo = FX ? (sc > 0.f ? M : kNegInf) : m;
-      if (lane < 16) xw[w * 64 + 16 * f + lane] = f32x2{mo, sc};
-    }
+    fwd64_cols<FX>(acc, p.y_scale, [&](int f, float m, float sc) {
+      if (lane < 16) xw[w * 64 + 16 * f + lane] = f32x2{m, sc};
+    });
     __syncthreads();
     if (tid < 64) {
       f32x2 v = xw[tid];
@@ -2470,65 +2492,30 @@ __global__ __launch_bounds__(256) void sk_reduce_kernel(const SimParams p, float
       for (int j = 0; j < 4; ++j) v[j] += x[u][j] * k;
     }
   }
-  if (p.sc) {  // kept cosines (canonical fragment order), before the masks
-    TS* st = reinterpret_cast<TS*>(p.sc) + (long long)tile * kTileElems;
-    if constexpr (sizeof(TS) == 2) {
-#pragma unroll
-      for (int np = 0; np < 2; ++np) {
-        union { TS h[8]; u32x4 u; } pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          pk.h[r] = from_f32<TS>(v[2 * np][r]);
-          pk.h[4 + r] = from_f32<TS>(v[2 * np + 1][r]);
-        }
-        *reinterpret_cast<u32x4*>(st + sc_unit(s16, 64 * w + 32 * np, lane) * 8) = pk.u;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        *reinterpret_cast<f32x4*>(st + (((s16 >> 4) * 16 + ((64 * w + 16 * j) >> 4)) * 64 + lane) * 4) = v[j];
-    }
-  }
-  const int r0 = mt * kTile, c0 = (nt * kTile) % p.Rpad;
-  const int D0 = r0 - c0, D1 = D0 + p.n_half, D2 = D0 - p.n_half;
-  const float sc_ = p.acc_scale, M = p.y_scale;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int tr = s16 + r4 + r, tc = 64 * w + 16 * j + c1, gi = r0 + tr, d = tc - tr;
-      const bool drop = (gi >= p.R) | (c0 + tc >= p.R) | (d == D0) | ((d == D1) & (gi < p.n_half)) |
-                        ((d == D2) & (gi >= p.n_half));
-      v[j][r] = drop ? kNegInf : v[j][r] * sc_;
-    }
-  // row partials over this wave's 64 columns (the 16 lanes of a DPP row), merged over the waves
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float m = M;
-    if constexpr (!FX) m = row16_max(fmaxf(fmaxf(v[0][r], v[1][r]), fmaxf(v[2][r], v[3][r])));
-    const float ms = (m == kNegInf) ? 0.f : m;
-    float sr = (fast_exp2(v[0][r] - ms) + fast_exp2(v[1][r] - ms)) + (fast_exp2(v[2][r] - ms) + fast_exp2(v[3][r] - ms));
-    sr = row16_sum(sr);
-    if (c1 == 0) {
-      red[w][r4 + r][0] = FX ? (sr > 0.f ? M : kNegInf) : m;
-      red[w][r4 + r][1] = sr;
-    }
-  }
+  // this wave's 16 rows x 64 columns of the strip: kept cosines, masks and partials by
+  // fwd64_epilogue. Split-K runs own-block launches only (launch_fwd_stats: pieces > 0 needs
+  // diag_tail > 0 and no part_x), so the pair rule applies without a test of the tile kind.
+  const int r0 = mt * kTile;
+  const pair::TileMask tm(p.R, p.n_half, r0, (nt * kTile) % p.Rpad);
+  TS* const st = p.sc ? reinterpret_cast<TS*>(p.sc) + (long long)tile * kTileElems : nullptr;
   const bool sym = kind == kTileSymOff;
-  if (sym) {  // this strip's column partials (16 rows): the 4 rows of a lane, lanes l ^ 16, 32, 48
+  // row partials over this wave's 64 columns (the 16 lanes of a DPP row), merged over the waves
+  // below; for a kTileSymOff tile this strip's column partials too (16 rows: the 4 rows of a lane,
+  // lanes l ^ 16, 32, 48)
+  fwd64_epilogue<TS, FX>(
+      v, tm, s16, 64 * w, lane, st, p.acc_scale, p.y_scale, [&](int r, float m, float sr) {
+        if (c1 == 0) {
+          red[w][r4 + r][0] = m;
+          red[w][r4 + r][1] = sr;
+        }
+      });
+  if (sym) {
     const auto crs = __builtin_amdgcn_make_buffer_rsrc(colp + (size_t)tile * kSkColpTile, 0, kSkColpTile * 8, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float m = M;
-      if constexpr (!FX) m = xrow_max(fmaxf(fmaxf(v[j][0], v[j][1]), fmaxf(v[j][2], v[j][3])));
-      const float ms = (m == kNegInf) ? 0.f : m;
-      float sc2 = (fast_exp2(v[j][0] - ms) + fast_exp2(v[j][1] - ms)) + (fast_exp2(v[j][2] - ms) + fast_exp2(v[j][3] - ms));
-      sc2 = xrow_sum(sc2);
-      const float mo = FX ? (sc2 > 0.f ? M : kNegInf) : m;
+    fwd64_cols<FX>(v, p.y_scale, [&](int j, float m, float sc2) {
       if (lane < 16)  // write-through (sc1): read by the tile's last strip block on any XCD
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(mo), __float_as_uint(sc2)}, crs,
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(m), __float_as_uint(sc2)}, crs,
                                               (strip * kTile + 64 * w + 16 * j + c1) * 8, 0, 16);
-    }
+    });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();

@@ -25,6 +25,7 @@
 //               them in split order. Replaces src/ntxent_kernel.cu:205-239.
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
+#include "pair_mask.h"
 
 #include <algorithm>
 
@@ -197,13 +198,12 @@ __global__ __launch_bounds__(kSmallThreads) void small_fwd_kernel(const SmallPar
     for (int r = 0; r < 4; ++r) {
       const int row_t = 32 * wr + 16 * mi + 4 * g + r;
       const int gi = I * kSmallTile + row_t;
-      const int gpos = gi < p.n_half ? gi + p.n_half : gi - p.n_half;
+      const int gpos = pair::partner(gi, p.n_half);
       float y[2];
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int gj = J * kSmallTile + 32 * wc + 16 * ni + r16;
-        const bool drop = (gi >= p.R) | (gj >= p.R) | (gj == gi) | (gj == gpos);
-        y[ni] = drop ? kNegInf : acc[mi][ni][r] * M;
+        y[ni] = pair::is_masked(gi, gj, p.R, p.n_half) ? kNegInf : acc[mi][ni][r] * M;
         // the positive pair lives in exactly one tile of the row: publish its logit (write-through,
         // read by the row block's last arriver after the ticket below)
         if (FUSE && gj == gpos && gi < p.R) __hip_atomic_store(p.ypos + gi, acc[mi][ni][r] * M, __ATOMIC_RELAXED,
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(kSmallThreads) void small_bwd_kernel(const SmallPar
   __syncthreads();
   const int il = 16 * w + r16;            // tile-local row of this lane in S^T / C
   const int gi = I * kSmallTile + il;
-  const int gpos = gi < p.n_half ? gi + p.n_half : gi - p.n_half;
+  const int gpos = pair::partner(gi, p.n_half);
   const float lse_i = s_lse[gi], a_i = s_a[gi];
   const bool row_ok = gi < p.R;
   const float M = p.y_scale;

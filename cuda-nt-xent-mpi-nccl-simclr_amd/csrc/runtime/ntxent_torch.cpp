@@ -29,6 +29,7 @@
 #include "ntxent/ntxent.h"
 #include "ntxent/step.h"
 #include "ntxent/sym_step.h"
+#include "../kernels/pair_mask.h"  // the pair rule the kernels inline (pair_* bindings below)
 
 namespace ntxent {
 namespace th {
@@ -1577,6 +1578,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return r;
   }, py::arg("rows"), py::arg("dim"), py::arg("input"), py::arg("compute"), py::arg("keep_cos") = true,
      py::arg("num_cus") = 256);
+  // The NT-Xent pair rule of the kernels (kernels/pair_mask.h) on the host, for
+  // tests/test_pair_mask_cpu.py: thin wrappers, the loops over a whole square included.
+  m.def("pair_partner", [](int i, int n_half) { return ntxent::pair::partner(i, n_half); });
+  m.def("pair_negative_matrix", [](int R, int n_half, int n) {  // [n][n]: is_negative(i, j)
+    auto out = at::empty({n, n}, at::kBool);
+    bool* o = out.data_ptr<bool>();
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < n; ++j) o[(size_t)i * n + j] = ntxent::pair::is_negative(i, j, R, n_half);
+    return out;
+  });
+  // [n][n]: TileMask::drop of every element, each through the tile x tile tile that holds it
+  m.def("pair_drop_matrix", [](int R, int n_half, int n, int tile, bool diag) {
+    auto out = at::empty({n, n}, at::kBool);
+    bool* o = out.data_ptr<bool>();
+    for (int r0 = 0; r0 < n; r0 += tile)
+      for (int c0 = 0; c0 < n; c0 += tile) {
+        const ntxent::pair::TileMask tm(R, n_half, r0, c0);
+        for (int tr = 0; tr < tile && r0 + tr < n; ++tr)
+          for (int tc = 0; tc < tile && c0 + tc < n; ++tc) o[(size_t)(r0 + tr) * n + c0 + tc] = tm.drop(tr, tc, diag);
+      }
+    return out;
+  }, py::arg("R"), py::arg("n_half"), py::arg("n"), py::arg("tile"), py::arg("diag") = true);
+  m.def("pair_window_plain", &ntxent::pair::window_plain, py::arg("r_lo"), py::arg("nr"), py::arg("c_lo"), py::arg("nc"),
+        py::arg("own0"), py::arg("R"), py::arg("n_half"), py::arg("c_local"));
+  m.def("pair_tile_near", [](int R, int n_half, int r0, int c0) { return ntxent::pair::TileMask(R, n_half, r0, c0).near(); });
+  m.def("pair_fragment_near", [](int R, int n_half, int r0, int c0, int off) {
+    return ntxent::pair::TileMask(R, n_half, r0, c0).fragment_near(off);
+  });
   m.attr("TILE") = ntxent::kTile;
   m.attr("K_STEP_BYTES") = ntxent::kKStepBytes;
 }
