@@ -11,6 +11,8 @@ from .ops import (  # noqa: F401,E402
     InfoNCELoss,
     NTXentFunction,
     NTXentLoss,
+    SigmoidFunction,
+    SigmoidLoss,
     backward,
     check_matrix_core_support,
     check_tensor_core_support,
@@ -20,4 +22,5 @@ from .ops import (  # noqa: F401,E402
     info_nce_loss,
     ntxent_loss,
     positive_rank,
+    sigmoid_loss,
 )

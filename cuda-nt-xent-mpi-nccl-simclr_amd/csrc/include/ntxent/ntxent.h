@@ -485,6 +485,42 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
                        void* zt, hipStream_t stream);
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream);
 
+// ---- pairwise sigmoid loss, the SigLIP form (kernels/xview_kernels.hip) -------------------------------
+// One rank's rows (g.world == 1), zq = launch_prep's unit rows of the stacked views, n = R/2 pairs:
+//   x_ij = a_i . b_j / tau + bias,  loss = 1/n sum_ij softplus(-s_ij x_ij),  s_ii = +1, s_ij = -1 (i != j)
+// over all n x n pairs of the block Z1 Z2^T. tau is the geometry's; bias is passed by value.
+//   launch_xview_sigmoid_fwd : the tile GEMM whose epilogue sums the tile's softplus terms (log1p form)
+//     into one fp64 partial in `scratch` (xview_sigmoid_scratch_bytes, 8-byte aligned, no
+//     initialisation needed), then their fixed-order sum: loss[0]. Two launches.
+//   launch_xview_sigmoid_coef: both views' transposed rows into `zt` (xview_zt_bytes) and the
+//     coefficient block C = 2 G into `coef` (xview_coef_bytes; planes as launch_xview_coef), with
+//     G_ij = sigmoid(x_ij) and G_ii = -sigmoid(-x_ii); the waves' fp32 sums of C into bias_part
+//     (xview_sigmoid_bias_part_bytes). launch_xview_dz, launch_norm_bwd (dot_out) and launch_tau_grad
+//     then give dh and dL/dtau as they are: the factor 2 makes their 1 / (R tau) and 1 / (2 R tau^2)
+//     this loss's 1 / (n tau) and 1 / (n tau^2).
+//   launch_xview_sigmoid_bias_grad: dbias[0] = grad_out[0] * sum(bias_part) / (2 n) = grad_out dL/dbias,
+//     one block, fp64, fixed order.
+// No atomics, no host sync: deterministic and capturable.
+size_t xview_sigmoid_scratch_bytes(const Geometry& g);
+size_t xview_sigmoid_bias_part_bytes(const Geometry& g);
+void launch_xview_sigmoid_fwd(DType comp, const void* zq, const Geometry& g, float bias, float* loss, void* scratch,
+                              hipStream_t stream, const float* pos_cos = nullptr);
+void launch_xview_sigmoid_coef(DType comp, const void* zq, const Geometry& g, float bias, void* coef, void* zt,
+                               float* bias_part, hipStream_t stream, const float* pos_cos = nullptr);
+// pos_cos (optional, [R/2]): the pairs' cosines a_i . b_i, taken for the diagonal x_ii by both launches
+// above in place of the tile's sum. launch_xview_sigmoid_pos forms them from the input rows h ([R][dim],
+// dtype `in`) and launch_prep's inv in fp32 (products of the fp32 unit rows, summed in fp64): for
+// 16-bit plans, whose unit rows' rounding would otherwise shift every x_ii, the N terms that carry the
+// loss and the bias and temperature gradients, with nothing to cancel the shift. An fp32 plan's tile sum
+// is of that precision already.
+// This is a third kernel and one more launch per direction beside the two epilogues. With it the loss, dL/dbias, dL/dtau's coefficients and the diagonal of C all see the fp32
+// x_ii, while the two dZ products still multiply C by the 16-bit unit rows: dh is the gradient of the
+// returned loss up to the 16-bit rounding of those rows (as in every 16-bit plan here), not to fp32.
+void launch_xview_sigmoid_pos(DType in, const void* h, const float* inv, const Geometry& g, float* pos_cos,
+                              hipStream_t stream);
+void launch_xview_sigmoid_bias_grad(const float* bias_part, const float* grad_out, float* dbias, const Geometry& g,
+                                    hipStream_t stream);
+
 // ---- distributed cross-view InfoNCE: rank g.rank of g.world ranks ---------------------------------
 // The global-batch form of the loss above. Every rank holds n = R/2 pairs; the global batch in pair
 // order is [a_0; ..; a_{W-1}; b_0; ..; b_{W-1}] (N = W n pairs). zq_all [W * Rpad][ld_k] holds every

@@ -51,6 +51,11 @@
 //     view-2 rows' partials, slot I (half the forward FLOPs of two sides);
 //   - the backward stores G once (side 0) and xview_gt_kernel transposes the planes in place between
 //     the two dZ products, instead of a second coefficient pass.
+//
+// The pairwise sigmoid loss (the SigLIP form, one GPU) is two more epilogues of the same tile GEMM,
+// xview_sigmoid_fwd_kernel and xview_sigmoid_coef_kernel (below, beside the family): no LSE, no
+// column partials; its coefficient block goes through the same transposes and dZ products. 16-bit
+// plans take the positives' cosines from the fp32 unit rows (xview_sigmoid_pos_kernel).
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
 #include "host_common.h"
@@ -474,6 +479,209 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
     }
 }
 
+// ---- pairwise sigmoid loss (the SigLIP form), one GPU ------------------------------------------------
+// x_ij = a_i . b_j / tau + bias over the n x n pairs of the block Z1 Z2^T (side 0's nT x nT tiles of
+// world 1, rank 0: every pair is computed once); the positive of row i is column i:
+//   loss = 1/n sum_ij softplus(-s_ij x_ij),  s_ii = +1, s_ij = -1 otherwise.
+// With G_ij = sigmoid(x_ij) (i != j) and G_ii = -sigmoid(-x_ii) the coefficient block is C = 2 G: the
+// factor (a power of two: exact) makes launch_norm_bwd's grad_out / (R tau) the loss's 1 / (n tau) and
+// launch_tau_grad's -(1 / (2 R tau^2)) sum_i dot_i over both views' rows dL/dtau, so the dZ products,
+// the normalisation backward and the temperature gradient serve as they are.
+struct XvSigParams {
+  XvParams x;        // the tile GEMM's operands; the coefficient pass: gbuf / ldg / plane_bytes as well
+  // x_ij in log2 units = cos_ij * scale2 + bias2, formed in fp64 and rounded to fp32 once per pair: an
+  // fp32 scale and bias would be off by their own rounding in the same direction for every pair, which
+  // no sum over the pairs averages out (the bias gradient's sum least of all)
+  double scale2;     // log2(e) / tau
+  double bias2;      // log2(e) * bias
+  double* lpart;    // forward: [nT * nT] the tiles' sums of softplus terms
+  float* bias_part;  // coefficient pass: [nT * nT][4] the waves' sums of C = 2 G
+  // 16-bit plans: [n] the pairs' cosines a_i . b_i from the input rows in fp32
+  // (xview_sigmoid_pos_kernel), taken for the diagonal in place of the tile's sum; null: the tile's.
+  // The N positives carry the loss, dL/dbias and dL/dtau once bias pushes the negatives down, every
+  // x_ii enters with weight 1 / N, and the mean shift of cos_ii from rounding the unit rows to 16 bits
+  // (2.6e-5 in bf16) goes through undiminished: no normaliser cancels it as a softmax loss's does.
+  const float* pos_cos;
+};
+
+// cos[i] = z_i . z_{i + n} of the fp32 unit rows z = h * inv, the operands an fp32 plan has (so rows
+// that are exact there, one-hot ones, are exact here): one wave per pair, the products summed in fp64
+// in a fixed order (lane, then the wave's lanes).
+template <typename Tin>
+__global__ __launch_bounds__(256) void xview_sigmoid_pos_kernel(const Tin* __restrict__ h, const float* __restrict__ inv,
+                                                                float* __restrict__ cos, int n, int d) {
+  const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;  // whole wave
+  const Tin* a = h + (long long)i * d;
+  const Tin* b = h + (long long)(i + n) * d;
+  const float ia = inv[i], ib = inv[i + n];
+  double s = 0.0;
+#pragma unroll 8  // the loads of eight steps in flight; the sum keeps its order
+  for (int e = lane; e < d; e += 64) s += (double)(to_f32<Tin>(a[e]) * ia) * (double)(to_f32<Tin>(b[e]) * ib);
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);
+  if (lane == 0) cos[i] = (float)s;
+}
+
+// The pairs' cosines of the rows of a diagonal tile this lane holds (pos_cos given), else zeros.
+__device__ __forceinline__ void xv_sig_load_pos(const XvSigParams& ps, bool diag, int row0, int g, float (&pc)[4][4]) {
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pc[mi][r] = 0.f;
+  if (diag && ps.pos_cos) {  // block-uniform
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int li = row0 + 16 * mi + 4 * g + r;
+        if (li < ps.x.n) pc[mi][r] = ps.pos_cos[li];
+      }
+  }
+}
+
+// Forward: tile (I, Jl)'s sum of softplus terms, natural-log units. softplus(t) = max(t, 0) +
+// log1p(e^-|t|): the log1p form keeps a negative's term (e^-20 at cos = -1, tau = 0.1, bias = -10)
+// where log(1 + e) would return 0. Rows and columns at or beyond n contribute nothing, selected by
+// index (a pad column has cos = 0 and would add softplus(bias)). Fixed order: a lane's 64 terms, the
+// wave's 64 lanes, the four waves; fp64 from the lane on, so the loss is rounded to fp32 once, at
+// its end. One partial per tile, no atomics.
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvSigParams ps) {
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
+  lds_char* lds = (lds_char*)smem;
+  const XvParams& p = ps.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int I = b / p.nT, Jl = b - I * p.nT;
+  const int n = p.n;
+
+  f32x4 acc[4][4];
+  xv_tile_gemm<T>(p, 0, I, 0, Jl, lds, acc);
+
+  int cl[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+  const bool fine_pos = ps.pos_cos != nullptr;
+  float pc[4][4];
+  xv_sig_load_pos(ps, Jl == I, I * kXvTile + 64 * wr, g, pc);
+  double sum = 0.0;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int li = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const bool in = (li < n) & (cl[ni] < n);
+        const bool pos = cl[ni] == li;  // only in a diagonal tile (Jl == I)
+        const double x2 = fma((double)((pos & fine_pos) ? pc[mi][r] : acc[mi][ni][r]), ps.scale2, ps.bias2);
+        const double t2 = pos ? -x2 : x2;  // -s_ij x_ij
+        const double sp = fmax(t2, 0.0) * 0.6931471805599453 + (double)log1pf(fast_exp2(-fabsf((float)t2)));
+        sum += in ? sp : 0.0;
+      }
+    }
+  // the wave's lanes, then the four waves (the staging images are free: xv_tile_gemm ended with a barrier)
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) sum += __shfl_xor(sum, m, 64);
+  double* s_w = reinterpret_cast<double*>(smem);
+  if (lane == 0) s_w[w] = sum;
+  __syncthreads();
+  if (tid == 0) ps.lpart[b] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+
+// Coefficient pass: the same tile, stored as xview_side_coef_kernel stores G (one fp32 plane, or the
+// residual plane scaled by kXvLoScale and the hi plane; exact zeros outside the valid rows and
+// columns), with C = 2 G: 2 sigmoid(x) = 2 / (1 + e^-x) off the diagonal and, formed directly,
+// -2 sigmoid(-x) = -2 / (1 + e^x) on it (an overflowing exponential gives the exact limit 0). The bias
+// gradient's partials are taken from the fp32 values before they are rounded to the planes: the plane
+// image fills the whole __shared__ object, so every wave reduces in its registers and stores one
+// fp32 partial to bias_part[tile][wave].
+template <typename T>
+__global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const XvSigParams ps) {
+  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
+  lds_char* lds = (lds_char*)smem;
+  const XvParams& p = ps.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int I = b / p.nT, Jl = b - I * p.nT;
+  const int n = p.n;
+
+  f32x4 acc[4][4];
+  xv_tile_gemm<T>(p, 0, I, 0, Jl, lds, acc);
+
+  constexpr bool kSplit = sizeof(T) == 2;
+  constexpr int kPlaneElems = kXvTile * kXvTile;
+  T* s_g = reinterpret_cast<T*>(smem);
+  int cl[4];
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+  const bool fine_pos = ps.pos_cos != nullptr;
+  float pc[4][4];
+  xv_sig_load_pos(ps, Jl == I, I * kXvTile + 64 * wr, g, pc);
+  float bsum = 0.f;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int rt = 64 * wr + 16 * mi + 4 * g + r;
+      const int li = I * kXvTile + rt;
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) {
+        const bool ok = (li < n) & (cl[ni] < n);
+        const bool pos = cl[ni] == li;
+        const float x2 = (float)fma((double)((pos & fine_pos) ? pc[mi][r] : acc[mi][ni][r]), ps.scale2, ps.bias2);
+        const float c = (pos ? -2.f : 2.f) / (1.f + fast_exp2(pos ? x2 : -x2));
+        // a select, not a product: zeros outside the valid rows and columns
+        const float v = ok ? c : 0.f;
+        bsum += v;
+        const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
+        const T hi = from_f32<T>(v);
+        if constexpr (kSplit) {
+          s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
+          s_g[kPlaneElems + at] = hi;
+        } else {
+          s_g[at] = hi;
+        }
+      }
+    }
+  bsum = wave_sum(bsum);
+  if (lane == 0) ps.bias_part[b * 4 + w] = bsum;
+  __syncthreads();
+  // 16-byte chunks, rows contiguous, as xview_side_coef_kernel
+  constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
+  constexpr int kCpp = kCpr * kXvTile;
+  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)Jl * kXvTile * (int)sizeof(T);
+#pragma unroll
+  for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
+    const int idx = c * kXvThreads + tid;
+    const int plane = idx / kCpp, in = idx - plane * kCpp;
+    const int row = in / kCpr, cc = in - row * kCpr;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
+    *reinterpret_cast<u32x4*>(gt + plane * p.plane_bytes + (long long)row * p.ldg + cc * 16) = v;
+  }
+}
+
+// dbias[0] = grad_out[0] * (sum of the `count` partials of C = 2 G) / (2 n). One block: thread t sums
+// partials t, t + 1024, ... in order, then a fixed halving tree (fp64): deterministic, no atomics.
+__global__ __launch_bounds__(kXvSumThreads) void xview_sigmoid_bias_kernel(const float* __restrict__ part, int count,
+                                                                           const float* __restrict__ grad_out,
+                                                                           double denom, float* __restrict__ dbias) {
+  __shared__ double red[kXvSumThreads];
+  double t = 0.0;
+  for (int i = threadIdx.x; i < count; i += kXvSumThreads) t += (double)part[i];
+  red[threadIdx.x] = t;
+  __syncthreads();
+#pragma unroll
+  for (int n = kXvSumThreads / 2; n > 0; n >>= 1) {
+    if ((int)threadIdx.x < n) red[threadIdx.x] += red[threadIdx.x + n];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dbias[0] = (float)((double)grad_out[0] * red[0] / denom);
+}
+
 }  // namespace dev
 
 namespace {
@@ -637,6 +845,80 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
     q.side = 1;
     hipLaunchKernelGGL((dev::xview_dz_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, q);
   });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+// ---- pairwise sigmoid loss, one GPU -------------------------------------------------------------------
+namespace {
+dev::XvSigParams xv_sig_params(DType comp, const void* zq, const Geometry& g, float bias, const std::string& who) {
+  dev::XvSigParams ps{};
+  ps.x = xv_params_one(comp, zq, g, who);
+  ps.scale2 = (double)g.inv_temp * 1.4426950408889634;
+  ps.bias2 = (double)bias * 1.4426950408889634;
+  return ps;
+}
+inline size_t xv_sig_tiles(const Geometry& g) {
+  const size_t nT = (size_t)(xv_npad(g) / dev::kXvTile);
+  return nT * nT;
+}
+}  // namespace
+
+size_t xview_sigmoid_scratch_bytes(const Geometry& g) { return xv_sig_tiles(g) * sizeof(double); }
+size_t xview_sigmoid_bias_part_bytes(const Geometry& g) { return xv_sig_tiles(g) * 4 * sizeof(float); }
+
+void launch_xview_sigmoid_pos(DType in, const void* h, const float* inv, const Geometry& g, float* pos_cos,
+                              hipStream_t stream) {
+  NTXENT_CHECK(h && inv && pos_cos, "xview_sigmoid_pos: null buffer");
+  NTXENT_CHECK(in != DType::FP8 && g.world == 1, "xview_sigmoid_pos: fp32 | fp16 | bf16 rows of one rank");
+  const int n = g.rows / 2;
+  dispatch_comp(in, [&](auto tin) {
+    using Tin = decltype(tin);
+    hipLaunchKernelGGL((dev::xview_sigmoid_pos_kernel<Tin>), dim3((n + 3) / 4), dim3(256), 0, stream,
+                       static_cast<const Tin*>(h), inv, pos_cos, n, g.dim);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_sigmoid_fwd(DType comp, const void* zq, const Geometry& g, float bias, float* loss, void* scratch,
+                              hipStream_t stream, const float* pos_cos) {
+  NTXENT_CHECK(zq && loss && scratch, "xview_sigmoid_fwd: null buffer");
+  dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, "xview_sigmoid_fwd");
+  ps.pos_cos = pos_cos;
+  ps.lpart = static_cast<double*>(scratch);
+  const int ntiles = (int)xv_sig_tiles(g);
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, ps);
+  });
+  // the tiles' partials in a fixed order, over the n pairs
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, ps.lpart, ntiles,
+                     (double)(g.rows / 2), loss, nullptr);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_sigmoid_coef(DType comp, const void* zq, const Geometry& g, float bias, void* coef, void* zt,
+                               float* bias_part, hipStream_t stream, const float* pos_cos) {
+  NTXENT_CHECK(zq && coef && zt && bias_part, "xview_sigmoid_coef: null buffer");
+  dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, "xview_sigmoid_coef");
+  ps.pos_cos = pos_cos;
+  const int np = xv_npad(g);
+  ps.x.gbuf = static_cast<char*>(coef);
+  ps.x.ldg = (long long)np * (long long)dtype_size(comp);
+  ps.x.plane_bytes = (long long)np * ps.x.ldg;
+  ps.bias_part = bias_part;
+  xv_launch_zt(comp, zq, g, zt, stream);
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<decltype(tc)>), dim3((int)xv_sig_tiles(g)), dim3(dev::kXvThreads), 0,
+                       stream, ps);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_sigmoid_bias_grad(const float* bias_part, const float* grad_out, float* dbias, const Geometry& g,
+                                    hipStream_t stream) {
+  NTXENT_CHECK(bias_part && grad_out && dbias, "xview_sigmoid_bias_grad: null buffer");
+  NTXENT_CHECK(g.world == 1, "xview_sigmoid_bias_grad: one rank only");
+  hipLaunchKernelGGL(dev::xview_sigmoid_bias_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, bias_part,
+                     (int)(4 * xv_sig_tiles(g)), grad_out, 2.0 * (double)(g.rows / 2), dbias);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 

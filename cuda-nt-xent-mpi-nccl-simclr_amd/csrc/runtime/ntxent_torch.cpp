@@ -401,6 +401,80 @@ std::tuple<at::Tensor, at::Tensor> xview_backward_tau(const at::Tensor& h, const
   return {r.first, r.second};
 }
 
+// ---- pairwise sigmoid loss, the SigLIP form (kernels/xview_kernels.hip) ----------------------------
+// Stacked views h = [h1; h2] on the current stream: the row prologue and the N x N tile GEMM with the
+// softplus epilogue. The compute dtype resolves as for xview_forward ("fp8" computes in fp16).
+// Returns {loss, inv}: nothing else needs saving (no normaliser; the backward runs the prologue again).
+// 16-bit plans: the pairs' cosines from the input rows in fp32 (launch_xview_sigmoid_pos), [R/2];
+// undefined for fp32 plans. The forward and the backward form them from the same h and inv: the
+// same bits.
+static at::Tensor sigmoid_pos_cos(const at::Tensor& h, const at::Tensor& inv, DType comp, const Geometry& g) {
+  if (comp == DType::F32) return at::Tensor();
+  auto pos = at::empty({g.rows / 2}, opts(h, at::kFloat));
+  launch_xview_sigmoid_pos(to_dtype(h.scalar_type()), h.data_ptr(), inv.data_ptr<float>(), g, pos.data_ptr<float>(),
+                           cur_stream(h));
+  return pos;
+}
+
+std::vector<at::Tensor> xview_sigmoid_forward(const at::Tensor& h, double T, double bias, const std::string& compute) {
+  check_input(h, "h");
+  check_stacked(h);
+  const at::DeviceGuard guard(h.device());
+  const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
+  auto P = xview_plan(h, T, comp);
+  const Geometry& g = P->g;
+  const auto st = prep(h, *P, c10::nullopt, c10::nullopt);  // {zq, inv, -, -}
+  auto scratch = at::empty({(long)(xview_sigmoid_scratch_bytes(g) / 8)}, opts(h, at::kDouble));
+  auto loss = at::empty({}, opts(h, at::kFloat));
+  const at::Tensor pos = sigmoid_pos_cos(h, st[1], comp, g);
+  launch_xview_sigmoid_fwd(comp, st[0].data_ptr(), g, (float)bias, loss.data_ptr<float>(), scratch.data_ptr(),
+                           cur_stream(h), pos.defined() ? pos.data_ptr<float>() : nullptr);
+  return {loss, st[1]};
+}
+
+// (dh, dtau, dbias), the last two times grad_out as 0-d fp32 tensors, undefined unless wanted; dh is
+// bitwise the same with or without them. Shaped like xview_backward_impl: buffers live only as long
+// as a stage needs them.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> xview_sigmoid_backward(const at::Tensor& h, const at::Tensor& inv,
+                                                                      const at::Tensor& grad_out, double T, double bias,
+                                                                      const std::string& compute, bool want_tau,
+                                                                      bool want_bias) {
+  check_input(h, "h");
+  check_stacked(h);
+  const at::DeviceGuard guard(h.device());
+  const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
+  auto P = xview_plan(h, T, comp);
+  const Geometry& g = P->g;
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat,
+               "xview_sigmoid_backward: inv must be float32 [rows] (xview_sigmoid_forward's output)");
+  const hipStream_t stream = cur_stream(h);
+  auto go = grad_scalar(grad_out);
+  auto coef = at::empty({(long)xview_coef_bytes(comp, g)}, opts(h, at::kByte));
+  auto zt = at::empty({(long)xview_zt_bytes(comp, g)}, opts(h, at::kByte));
+  auto bias_part = at::empty({(long)(xview_sigmoid_bias_part_bytes(g) / 4)}, opts(h, at::kFloat));
+  {
+    // the unit rows again, released once the coefficients exist (launch_prep is bitwise repeatable)
+    const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
+    const at::Tensor pos = sigmoid_pos_cos(h, inv, comp, g);
+    launch_xview_sigmoid_coef(comp, st[0].data_ptr(), g, (float)bias, coef.data_ptr(), zt.data_ptr(),
+                              bias_part.data_ptr<float>(), stream, pos.defined() ? pos.data_ptr<float>() : nullptr);
+  }
+  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
+  launch_xview_dz(comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
+  at::Tensor dot, dtau, dbias;
+  auto dh = xview_backward_tail(h, inv, go, dz, coef, zt, g, stream, &dot);
+  if (want_tau) {
+    dtau = at::empty({}, opts(h, at::kFloat));
+    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau.data_ptr<float>(), g, stream);
+  }
+  if (want_bias) {
+    dbias = at::empty({}, opts(h, at::kFloat));
+    launch_xview_sigmoid_bias_grad(bias_part.data_ptr<float>(), go.data_ptr<float>(), dbias.data_ptr<float>(), g,
+                                   stream);
+  }
+  return {dh, dtau, dbias};
+}
+
 // ---- distributed cross-view InfoNCE: stage ops (parallel/infonce.py and parallel/emulate.py call
 // the same three) ----------------------------------------------------------------------------------
 // P: this rank's plan (get_plan(R, d, W, r, ...), fp32 | fp16 | bf16); zq_all [W * Rpad, ld_k]: every
@@ -1490,6 +1564,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xview_forward", &xview_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto");
   m.def("xview_backward", &xview_backward);
   m.def("xview_backward_tau", &xview_backward_tau);
+  m.def("xview_sigmoid_forward", &xview_sigmoid_forward, py::arg("h"), py::arg("T"), py::arg("bias"),
+        py::arg("compute") = "auto");
+  m.def("xview_sigmoid_backward", &xview_sigmoid_backward);
   m.def("xview_dist_part_slots", [](const Plan& P) { return (long)(xview_part_bytes(P.g) / 8 / P.g.rows_pad); });
   m.def("xview_dist_coef_bytes", [](const Plan& P) { return (long)xview_coef_bytes(P.bwd(), P.g); });
   m.def("xview_dist_fwd", &xview_dist_fwd, py::arg("zq_all"), py::arg("plan"), py::arg("part"), py::arg("ypos"),

@@ -4,6 +4,8 @@
   python -m ntxent_amd.models.train --steps 50 --batch 256 --learnable-temperature true   # one GPU
   python -m ntxent_amd.models.train --steps 50 --batch 256 --metrics-every 10   # top-1 / top-5 every 10 steps
   python -m ntxent_amd.models.train --steps 50 --batch 256 --loss infonce   # cross-view (CLIP-form) loss, one GPU
+  python -m ntxent_amd.models.train --steps 50 --batch 256 --loss sigmoid --temperature 0.1 --learnable-bias true
+                                                       # pairwise sigmoid (SigLIP-form) loss, one GPU
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \\
       -m ntxent_amd.models.train --steps 200 --batch 512 --ckpt-dir ckpt/ --ckpt-every 50
 """
@@ -26,7 +28,7 @@ def build_parser() -> argparse.ArgumentParser:
     for f in dataclasses.fields(TrainConfig):
         name = "--" + f.name.replace("_", "-")
         if f.name == "loss":
-            ap.add_argument(name, choices=("ntxent", "infonce"), default=f.default)
+            ap.add_argument(name, choices=("ntxent", "infonce", "sigmoid"), default=f.default)
         elif f.type in ("bool", bool):
             ap.add_argument(name, type=lambda s: s.lower() in ("1", "true", "yes"), default=f.default)
         elif f.type in ("int", int):

@@ -28,6 +28,7 @@ import torch.distributed as dist
 
 from ..ops.infonce import InfoNCELoss
 from ..ops.ntxent import NTXentLoss
+from ..ops.sigmoid import SigmoidLoss
 from ..utils.checkpoint import latest_checkpoint, load_checkpoint, save_checkpoint
 from ..utils.memory import GPUMemoryTracker
 from ..utils.trace import trace_range
@@ -75,8 +76,13 @@ class TrainConfig:
     # ranks each rank ranks its own 2 x batch rows only (negatives = 2 x batch - 2).
     metrics_every: int = 0
     # ntxent: SimCLR's loss, every other row a negative. infonce: the cross-view (CLIP-form) loss,
-    # negatives from the other view only (InfoNCELoss); one GPU only.
+    # negatives from the other view only (InfoNCELoss); one GPU only. sigmoid: the pairwise sigmoid
+    # (SigLIP-form) loss of the two views (SigmoidLoss) with `bias`; one GPU only.
     loss: str = "ntxent"
+    bias: float = -10.0              # loss="sigmoid": the logit bias (SigLIP's initialisation)
+    # loss="sigmoid": the loss owns the parameter `bias`, trained in a parameter group of its own with
+    # no weight decay and no LARS adaptation
+    learnable_bias: bool = False
 
 
 def _dist():
@@ -132,11 +138,16 @@ class SimCLRTrainer:
         if cfg.learnable_temperature and self.world > 1:
             raise NotImplementedError("learnable_temperature is supported on one GPU only (world == 1): the "
                                       "distributed loss does not reduce the temperature gradient across ranks")
-        if cfg.loss not in ("ntxent", "infonce"):
-            raise ValueError("loss must be ntxent or infonce")
+        if cfg.loss not in ("ntxent", "infonce", "sigmoid"):
+            raise ValueError("loss must be ntxent, infonce or sigmoid")
         if cfg.loss == "infonce" and self.world > 1:
             raise NotImplementedError("loss='infonce' is supported on one GPU only (world == 1): the cross-view "
                                       "loss has no distributed form")
+        if cfg.loss == "sigmoid" and self.world > 1:
+            raise NotImplementedError("loss='sigmoid' is supported on one GPU only (world == 1): the pairwise "
+                                      "sigmoid loss has no distributed form")
+        if cfg.learnable_bias and cfg.loss != "sigmoid":
+            raise ValueError("learnable_bias belongs to loss='sigmoid'")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
@@ -161,12 +172,18 @@ class SimCLRTrainer:
         if cfg.loss == "infonce":
             self.loss_fn = InfoNCELoss(cfg.temperature, compute=cfg.compute,
                                        learnable_temperature=cfg.learnable_temperature).to(device)
+        elif cfg.loss == "sigmoid":
+            self.loss_fn = SigmoidLoss(cfg.temperature, cfg.bias, compute=cfg.compute,
+                                       learnable_temperature=cfg.learnable_temperature,
+                                       learnable_bias=cfg.learnable_bias).to(device)
         else:
             self.loss_fn = NTXentLoss(cfg.temperature, compute=cfg.compute, distributed=self.world > 1,
                                       negatives=cfg.negatives,
                                       learnable_temperature=cfg.learnable_temperature).to(device)
         if cfg.learnable_temperature:
             self.opt.add_param_group({"params": [self.loss_fn.log_temperature], "weight_decay": 0.0, "lars": False})
+        if cfg.learnable_bias:
+            self.opt.add_param_group({"params": [self.loss_fn.bias], "weight_decay": 0.0, "lars": False})
         self.base_lrs = [g["lr"] for g in self.opt.param_groups]
         self.data = SyntheticImages(cfg, device, self.rank)
         self.aug = AugmentConfig(out_size=cfg.image_size)
@@ -181,6 +198,9 @@ class SimCLRTrainer:
                 if cfg.learnable_temperature and "log_temperature" in st["extra"]:
                     with torch.no_grad():
                         self.loss_fn.log_temperature.fill_(float(st["extra"]["log_temperature"]))
+                if cfg.learnable_bias and "bias" in st["extra"]:
+                    with torch.no_grad():
+                        self.loss_fn.bias.fill_(float(st["extra"]["bias"]))
 
     def train_step(self) -> Dict:
         if self.stream is None:
@@ -222,6 +242,8 @@ class SimCLRTrainer:
                "images_per_s": cfg.batch * self.world / dt}
         if cfg.learnable_temperature:  # the temperature the next step uses
             rec["temperature"] = float(self.loss_fn.current_temperature().detach())
+        if cfg.learnable_bias:  # the bias the next step uses
+            rec["bias"] = float(self.loss_fn.bias.detach())
         if cfg.metrics_every > 0 and self.step % cfg.metrics_every == 0:
             with trace_range("simclr.metrics"):
                 m = self.loss_fn.metrics(z.detach(), topk=(1, 5))
@@ -240,6 +262,12 @@ class SimCLRTrainer:
                 del conf["metrics_every"]
             if cfg.loss == "ntxent":
                 del conf["loss"]
+            if cfg.learnable_bias:
+                extra["bias"] = float(self.loss_fn.bias.detach())
+            else:
+                del conf["learnable_bias"]
+            if cfg.bias == -10.0:
+                del conf["bias"]
             save_checkpoint(Path(cfg.ckpt_dir) / f"ckpt_{self.step}.pt", model=self.model, optimizer=self.opt,
                             step=self.step, extra=extra, rank=self.rank)
         return rec

@@ -13,3 +13,4 @@ from .ntxent import (  # noqa: F401
     ntxent_loss,
     resolve_compute,
 )
+from .sigmoid import SigmoidFunction, SigmoidLoss, sigmoid_loss  # noqa: F401

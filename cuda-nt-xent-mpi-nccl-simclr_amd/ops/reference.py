@@ -153,6 +153,48 @@ def info_nce_temperature_grad_analytic(h: torch.Tensor, temperature: float,
 
 
 # ---------------------------------------------------------------------------------------
+# Pairwise sigmoid loss (the SigLIP form): every one of the N x N pairs is a binary term.
+# ---------------------------------------------------------------------------------------
+def _sigmoid_pairs(h: torch.Tensor, temperature, bias):
+    """(A, B, inv, x) of stacked views: the unit towers and ``x_ij = a_i . b_j / tau + bias``."""
+    if h.dim() != 2 or h.shape[0] % 2:
+        raise ValueError("h must be [2N, d] with stacked views")
+    n = h.shape[0] // 2
+    z, inv = normalize(h)
+    return z[:n], z[n:], inv, z[:n] @ z[n:].t() / temperature + bias
+
+
+def sigmoid_loss(h: torch.Tensor, temperature=0.1, bias=-10.0) -> torch.Tensor:
+    """Autograd-capable pairwise sigmoid loss on stacked views ``h = [h1; h2]``:
+    ``(1 / N) sum_ij softplus(-s_ij x_ij)`` with ``s_ii = +1`` and ``s_ij = -1`` otherwise (SigLIP's
+    loss with ``t = 1 / tau``). ``temperature`` and ``bias`` may be floats or 0-d tensors."""
+    n = h.shape[0] // 2
+    _, _, _, x = _sigmoid_pairs(h, temperature, bias)
+    s = 2.0 * torch.eye(n, dtype=h.dtype, device=h.device) - 1.0
+    return torch.nn.functional.softplus(-s * x).sum() / n
+
+
+def sigmoid_backward_analytic(h: torch.Tensor, temperature: float, bias: float,
+                              grad_out: float | torch.Tensor = 1.0):
+    """Closed-form ``(dh, dtau, dbias)`` of ``sigmoid_loss`` (what the HIP backward implements). With
+    ``G_ij = sigmoid(x_ij)`` off the diagonal and ``G_ii = -sigmoid(-x_ii)`` (formed directly, not as
+    ``sigmoid - 1``): dL/dA = G B / (N tau), dL/dB = G^T A / (N tau), dL/dbias = sum G / N,
+    dL/dtau = -sum G o cos / (N tau^2); dL/dh = inv (dz - z (z . dz))."""
+    n = h.shape[0] // 2
+    tau = float(temperature)
+    a, b, inv, x = _sigmoid_pairs(h, tau, float(bias))
+    eye = torch.eye(n, dtype=torch.bool, device=h.device)
+    G = torch.where(eye, -torch.sigmoid(-x), torch.sigmoid(x))
+    go = torch.as_tensor(grad_out, dtype=h.dtype, device=h.device)
+    z = torch.cat([a, b], 0)
+    dz = torch.cat([G @ b, G.t() @ a], 0) * (go / (n * tau))
+    dot = (z * dz).sum(1, keepdim=True)
+    dh = inv.unsqueeze(1) * (dz - z * dot)
+    dtau = -go * (G * (a @ b.t())).sum() / (n * tau * tau)
+    return dh, dtau, go * G.sum() / n
+
+
+# ---------------------------------------------------------------------------------------
 # Contrastive metrics: the rank of each row's positive among its negatives.
 # ---------------------------------------------------------------------------------------
 def _negatives_mask(rows: int, device=None) -> torch.Tensor:
