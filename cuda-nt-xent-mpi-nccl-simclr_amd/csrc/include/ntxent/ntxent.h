@@ -400,7 +400,10 @@ void launch_norm_bwd(DType in, const float* slabs, int nslabs, const void* h,
 // dot of the fused dZ epilogue (NormFuse::dot, complete once the dZ launch has finished), or the
 // dot_out of launch_norm_bwd / launch_small_bwd. Rows at or beyond g.rows are not read. One block,
 // a fixed assignment of rows to threads and a fixed-order tree (fp64): deterministic, no atomics.
-void launch_tau_grad(const float* dot, const float* grad_out, float* dtau, const Geometry& g, hipStream_t stream);
+// share64 (with dtau null): the same number before its rounding to fp32, a rank's share of the global
+// dL/dtau: the shares are summed across ranks and rounded once.
+void launch_tau_grad(const float* dot, const float* grad_out, float* dtau, const Geometry& g, hipStream_t stream,
+                     double* share64 = nullptr);
 
 // ---- small-problem path (kernels/small_kernels.hip) -------------------------------------
 // Single-rank problems with R <= kSmallMaxRows and dim_k <= kSmallMaxDk in fp16/bf16: ONE
@@ -486,7 +489,7 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream);
 
 // ---- pairwise sigmoid loss, the SigLIP form (kernels/xview_kernels.hip) -------------------------------
-// One rank's rows (g.world == 1), zq = launch_prep's unit rows of the stacked views, n = R/2 pairs:
+// One GPU (g.world == 1), zq = launch_prep's unit rows of the stacked views, n = R/2 pairs:
 //   x_ij = a_i . b_j / tau + bias,  loss = 1/n sum_ij softplus(-s_ij x_ij),  s_ii = +1, s_ij = -1 (i != j)
 // over all n x n pairs of the block Z1 Z2^T. tau is the geometry's; bias is passed by value.
 //   launch_xview_sigmoid_fwd : the tile GEMM whose epilogue sums the tile's softplus terms (log1p form)
@@ -518,8 +521,33 @@ void launch_xview_sigmoid_coef(DType comp, const void* zq, const Geometry& g, fl
 // returned loss up to the 16-bit rounding of those rows (as in every 16-bit plan here), not to fp32.
 void launch_xview_sigmoid_pos(DType in, const void* h, const float* inv, const Geometry& g, float* pos_cos,
                               hipStream_t stream);
+// share64 (with dbias null): the same number before its rounding to fp32, a rank's share (below).
 void launch_xview_sigmoid_bias_grad(const float* bias_part, const float* grad_out, float* dbias, const Geometry& g,
-                                    hipStream_t stream);
+                                    hipStream_t stream, double* share64 = nullptr);
+
+// Rank g.rank of g.world ranks: the loss of the global batch [a_0; ..; b_{W-1}] of N = W n pairs, over
+// zq_all [W * Rpad][ld_k] as in the distributed InfoNCE below. The same two epilogue kernels; one GPU
+// above is their world = 1, side-0 case (same tile order, same partials, same planes: the same bits).
+//   launch_xview_sigmoid_dist_fwd : side 0's tiles (I, slot q, Jl) for the slots [q_lo, q_hi) except
+//     q_skip (-1: none): rows a_r against b of those slots. Only side 0: every global pair is computed
+//     exactly once, on the rank that holds a_i. Tile (I, q, Jl) writes lpart[(I * W + q) * nT + Jl]
+//     (xview_sigmoid_scratch_bytes, which reads g.world), so any split of the slots over launches
+//     fills one array. A pair is the positive only for q == rank and column == row; pos_cos as above,
+//     from this rank's h and inv.
+//   launch_xview_sigmoid_dist_loss: share[0] = sum(lpart) / N in fp64, fixed order: a SUM over the
+//     ranks, rounded to fp32 once, gives the loss.
+//   launch_xview_sigmoid_dist_coef: ONE side's n_pad x W n_pad block C = 2 G in launch_xview_dist_coef's
+//     layout (exact zeros outside the valid rows and columns). Side 1 swaps the operand roles (rows
+//     b_r, columns a of every slot) and so gives the rows of C^T directly. bias_part
+//     (xview_sigmoid_bias_part_bytes): with side 0 and only there, each pair counts once.
+// then launch_xview_dist_zt / launch_xview_dist_dz per side, launch_norm_bwd (dot_out), and the fp64
+// shares of launch_tau_grad (scale 1 / (2 * 2N tau^2) over the local dots) and
+// launch_xview_sigmoid_bias_grad (sum / 2N).
+void launch_xview_sigmoid_dist_fwd(DType comp, const void* zq_all, const Geometry& g, float bias, int q_lo, int q_hi,
+                                   int q_skip, double* lpart, hipStream_t stream, const float* pos_cos = nullptr);
+void launch_xview_sigmoid_dist_loss(const double* lpart, const Geometry& g, double* share, hipStream_t stream);
+void launch_xview_sigmoid_dist_coef(DType comp, const void* zq_all, const Geometry& g, float bias, int side, void* coef,
+                                    float* bias_part, hipStream_t stream, const float* pos_cos = nullptr);
 
 // ---- distributed cross-view InfoNCE: rank g.rank of g.world ranks ---------------------------------
 // The global-batch form of the loss above. Every rank holds n = R/2 pairs; the global batch in pair

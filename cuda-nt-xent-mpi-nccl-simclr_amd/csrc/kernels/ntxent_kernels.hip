@@ -858,7 +858,8 @@ __global__ __launch_bounds__(256) void dot_reduce_kernel(const float* __restrict
 constexpr int kTauGradThreads = 1024;
 __global__ __launch_bounds__(kTauGradThreads) void tau_grad_kernel(const float* __restrict__ dot, int rows,
                                                                    const float* __restrict__ grad_out, double scale,
-                                                                   float* __restrict__ dtau) {
+                                                                   float* __restrict__ dtau,
+                                                                   double* __restrict__ share64) {
   __shared__ double part[kTauGradThreads];
   double t = 0.0;
   for (int i = threadIdx.x; i < rows; i += kTauGradThreads) t += (double)dot[i];
@@ -869,7 +870,11 @@ __global__ __launch_bounds__(kTauGradThreads) void tau_grad_kernel(const float* 
     if ((int)threadIdx.x < n) part[threadIdx.x] += part[threadIdx.x + n];
     __syncthreads();
   }
-  if (threadIdx.x == 0) dtau[0] = (float)((double)grad_out[0] * scale * part[0]);
+  if (threadIdx.x == 0) {  // share64 (dtau null): a rank's share, summed across ranks before its one rounding
+    const double v = (double)grad_out[0] * scale * part[0];
+    if (dtau) dtau[0] = (float)v;
+    else share64[0] = v;
+  }
 }
 
 }  // namespace dev
@@ -1865,12 +1870,14 @@ void launch_dz_view(DType comp, const void* a, long long a_panel_tiles, const vo
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-void launch_tau_grad(const float* dot, const float* grad_out, float* dtau, const Geometry& g, hipStream_t stream) {
-  NTXENT_CHECK(dot != nullptr && grad_out != nullptr && dtau != nullptr, "tau_grad: null buffer");
+void launch_tau_grad(const float* dot, const float* grad_out, float* dtau, const Geometry& g, hipStream_t stream,
+                     double* share64) {
+  NTXENT_CHECK(dot != nullptr && grad_out != nullptr && (dtau != nullptr) != (share64 != nullptr),
+               "tau_grad: null buffer (one of dtau and share64)");
   const double tau = (double)g.temperature;
   const double scale = -1.0 / (2.0 * (double)g.global_rows * tau * tau);
   hipLaunchKernelGGL(dev::tau_grad_kernel, dim3(1), dim3(dev::kTauGradThreads), 0, stream, dot, g.rows, grad_out, scale,
-                     dtau);
+                     dtau, share64);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 

@@ -52,10 +52,13 @@
 //   - the backward stores G once (side 0) and xview_gt_kernel transposes the planes in place between
 //     the two dZ products, instead of a second coefficient pass.
 //
-// The pairwise sigmoid loss (the SigLIP form, one GPU) is two more epilogues of the same tile GEMM,
+// The pairwise sigmoid loss (the SigLIP form) is two more epilogues of the same tile GEMM,
 // xview_sigmoid_fwd_kernel and xview_sigmoid_coef_kernel (below, beside the family): no LSE, no
 // column partials; its coefficient block goes through the same transposes and dZ products. 16-bit
-// plans take the positives' cosines from the fp32 unit rows (xview_sigmoid_pos_kernel).
+// plans take the positives' cosines from the fp32 unit rows (xview_sigmoid_pos_kernel). Rank r of W:
+// the forward runs side 0's n x W n block alone (every global pair is computed once, on the rank
+// that holds its row a_i), the coefficient pass one side at a time as xview_side_coef_kernel; one
+// GPU is W = 1, side 0 of both, with the in-place transpose in place of side 1.
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
 #include "host_common.h"
@@ -479,10 +482,11 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
     }
 }
 
-// ---- pairwise sigmoid loss (the SigLIP form), one GPU ------------------------------------------------
-// x_ij = a_i . b_j / tau + bias over the n x n pairs of the block Z1 Z2^T (side 0's nT x nT tiles of
-// world 1, rank 0: every pair is computed once); the positive of row i is column i:
-//   loss = 1/n sum_ij softplus(-s_ij x_ij),  s_ii = +1, s_ij = -1 otherwise.
+// ---- pairwise sigmoid loss (the SigLIP form) ---------------------------------------------------------
+// x_ij = a_i . b_j / tau + bias over the n x W n pairs of this rank's view-1 rows against the view-2
+// rows of every slot (side 0's nT x W nT tiles: every global pair is computed once; one GPU is world
+// 1, rank 0); the positive of local row i is column i of the own slot:
+//   loss = 1/N sum_ij softplus(-s_ij x_ij),  s_ii = +1, s_ij = -1 otherwise,  N = W n.
 // With G_ij = sigmoid(x_ij) (i != j) and G_ii = -sigmoid(-x_ii) the coefficient block is C = 2 G: the
 // factor (a power of two: exact) makes launch_norm_bwd's grad_out / (R tau) the loss's 1 / (n tau) and
 // launch_tau_grad's -(1 / (2 R tau^2)) sum_i dot_i over both views' rows dL/dtau, so the dZ products,
@@ -494,8 +498,8 @@ struct XvSigParams {
   // no sum over the pairs averages out (the bias gradient's sum least of all)
   double scale2;     // log2(e) / tau
   double bias2;      // log2(e) * bias
-  double* lpart;    // forward: [nT * nT] the tiles' sums of softplus terms
-  float* bias_part;  // coefficient pass: [nT * nT][4] the waves' sums of C = 2 G
+  double* lpart;    // forward: [nT][world * nT] the tiles' sums of softplus terms, tile (I, q, Jl) at its place
+  float* bias_part;  // coefficient pass: [nT * world * nT][4] the waves' sums of C = 2 G; null (side 1): not stored
   // 16-bit plans: [n] the pairs' cosines a_i . b_i from the input rows in fp32
   // (xview_sigmoid_pos_kernel), taken for the diagonal in place of the tile's sum; null: the tile's.
   // The N positives carry the loss, dL/dbias and dL/dtau once bias pushes the negatives down, every
@@ -554,18 +558,24 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int I = b / p.nT, Jl = b - I * p.nT;
+  // side 0's tiles (I, slot q, Jl) of the launch's slots, as xview_fwd_kernel walks a side's
+  const int ncol = p.nq * p.nT;
+  const int I = b / ncol, jj = b - I * ncol;
+  int q = p.q_lo + jj / p.nT;
+  const int Jl = jj % p.nT;
+  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
   const int n = p.n;
+  const bool own = q == p.rank;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, 0, I, 0, Jl, lds, acc);
+  xv_tile_gemm<T>(p, 0, I, q, Jl, lds, acc);
 
   int cl[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
   const bool fine_pos = ps.pos_cos != nullptr;
   float pc[4][4];
-  xv_sig_load_pos(ps, Jl == I, I * kXvTile + 64 * wr, g, pc);
+  xv_sig_load_pos(ps, own && Jl == I, I * kXvTile + 64 * wr, g, pc);
   double sum = 0.0;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
@@ -575,7 +585,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const bool in = (li < n) & (cl[ni] < n);
-        const bool pos = cl[ni] == li;  // only in a diagonal tile (Jl == I)
+        const bool pos = own & (cl[ni] == li);  // only in a diagonal tile (Jl == I) of the own slot
         const double x2 = fma((double)((pos & fine_pos) ? pc[mi][r] : acc[mi][ni][r]), ps.scale2, ps.bias2);
         const double t2 = pos ? -x2 : x2;  // -s_ij x_ij
         const double sp = fmax(t2, 0.0) * 0.6931471805599453 + (double)log1pf(fast_exp2(-fabsf((float)t2)));
@@ -588,10 +598,13 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
   double* s_w = reinterpret_cast<double*>(smem);
   if (lane == 0) s_w[w] = sum;
   __syncthreads();
-  if (tid == 0) ps.lpart[b] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  // the tile's own place, whichever launch runs it: the sum's order does not depend on the split
+  if (tid == 0) ps.lpart[((long long)I * p.world + q) * p.nT + Jl] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
 }
 
-// Coefficient pass: the same tile, stored as xview_side_coef_kernel stores G (one fp32 plane, or the
+// Coefficient pass: tile (I, J) of side p.side's n_pad x W n_pad block (side 1: rows b_r against a of
+// every slot; x is symmetric in that swap, so these are the rows of C^T), stored as
+// xview_side_coef_kernel stores G (one fp32 plane, or the
 // residual plane scaled by kXvLoScale and the hi plane; exact zeros outside the valid rows and
 // columns), with C = 2 G: 2 sigmoid(x) = 2 / (1 + e^-x) off the diagonal and, formed directly,
 // -2 sigmoid(-x) = -2 / (1 + e^x) on it (an overflowing exponential gives the exact limit 0). The bias
@@ -606,11 +619,15 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int I = b / p.nT, Jl = b - I * p.nT;
+  // tile (I, J) of one side's n_pad x W n_pad block, as xview_side_coef_kernel
+  const int ncol = p.world * p.nT;
+  const int I = b / ncol, J = b - I * ncol;
+  const int q = J / p.nT, Jl = J - q * p.nT;
   const int n = p.n;
+  const bool own = q == p.rank;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, 0, I, 0, Jl, lds, acc);
+  xv_tile_gemm<T>(p, p.side, I, q, Jl, lds, acc);
 
   constexpr bool kSplit = sizeof(T) == 2;
   constexpr int kPlaneElems = kXvTile * kXvTile;
@@ -620,7 +637,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
   for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
   const bool fine_pos = ps.pos_cos != nullptr;
   float pc[4][4];
-  xv_sig_load_pos(ps, Jl == I, I * kXvTile + 64 * wr, g, pc);
+  xv_sig_load_pos(ps, own && Jl == I, I * kXvTile + 64 * wr, g, pc);
   float bsum = 0.f;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
@@ -631,7 +648,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const bool ok = (li < n) & (cl[ni] < n);
-        const bool pos = cl[ni] == li;
+        const bool pos = own & (cl[ni] == li);
         const float x2 = (float)fma((double)((pos & fine_pos) ? pc[mi][r] : acc[mi][ni][r]), ps.scale2, ps.bias2);
         const float c = (pos ? -2.f : 2.f) / (1.f + fast_exp2(pos ? x2 : -x2));
         // a select, not a product: zeros outside the valid rows and columns
@@ -648,12 +665,12 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
       }
     }
   bsum = wave_sum(bsum);
-  if (lane == 0) ps.bias_part[b * 4 + w] = bsum;
+  if (ps.bias_part && lane == 0) ps.bias_part[b * 4 + w] = bsum;  // side 0 only: each pair counts once
   __syncthreads();
   // 16-byte chunks, rows contiguous, as xview_side_coef_kernel
   constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
   constexpr int kCpp = kCpr * kXvTile;
-  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)Jl * kXvTile * (int)sizeof(T);
+  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
 #pragma unroll
   for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
     const int idx = c * kXvThreads + tid;
@@ -668,7 +685,8 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
 // partials t, t + 1024, ... in order, then a fixed halving tree (fp64): deterministic, no atomics.
 __global__ __launch_bounds__(kXvSumThreads) void xview_sigmoid_bias_kernel(const float* __restrict__ part, int count,
                                                                            const float* __restrict__ grad_out,
-                                                                           double denom, float* __restrict__ dbias) {
+                                                                           double denom, float* __restrict__ dbias,
+                                                                           double* __restrict__ share64) {
   __shared__ double red[kXvSumThreads];
   double t = 0.0;
   for (int i = threadIdx.x; i < count; i += kXvSumThreads) t += (double)part[i];
@@ -679,7 +697,11 @@ __global__ __launch_bounds__(kXvSumThreads) void xview_sigmoid_bias_kernel(const
     if ((int)threadIdx.x < n) red[threadIdx.x] += red[threadIdx.x + n];
     __syncthreads();
   }
-  if (threadIdx.x == 0) dbias[0] = (float)((double)grad_out[0] * red[0] / denom);
+  if (threadIdx.x == 0) {
+    const double v = (double)grad_out[0] * red[0] / denom;
+    if (dbias) dbias[0] = (float)v;
+    else share64[0] = v;
+  }
 }
 
 }  // namespace dev
@@ -848,18 +870,41 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-// ---- pairwise sigmoid loss, one GPU -------------------------------------------------------------------
+// ---- pairwise sigmoid loss -----------------------------------------------------------------------------
 namespace {
-dev::XvSigParams xv_sig_params(DType comp, const void* zq, const Geometry& g, float bias, const std::string& who) {
+// one: the one-GPU launches' geometry checks (world 1, rows padded to 256)
+dev::XvSigParams xv_sig_params(DType comp, const void* zq, const Geometry& g, float bias, const std::string& who,
+                               bool one = true) {
   dev::XvSigParams ps{};
-  ps.x = xv_params_one(comp, zq, g, who);
+  ps.x = one ? xv_params_one(comp, zq, g, who) : xv_params(comp, zq, g, who);
   ps.scale2 = (double)g.inv_temp * 1.4426950408889634;
   ps.bias2 = (double)bias * 1.4426950408889634;
   return ps;
 }
+// side 0's tiles of a rank: nT row tiles x world * nT column tiles
 inline size_t xv_sig_tiles(const Geometry& g) {
   const size_t nT = (size_t)(xv_npad(g) / dev::kXvTile);
-  return nT * nT;
+  return nT * (size_t)g.world * nT;
+}
+void xv_sig_launch_fwd(DType comp, const dev::XvSigParams& ps, hipStream_t stream) {
+  const int ntiles = ps.x.nT * ps.x.nq * ps.x.nT;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, ps);
+  });
+}
+// one side's block into coef: planes of n_pad rows, world * n_pad columns (xv_launch_coef's layout)
+void xv_sig_launch_coef(DType comp, dev::XvSigParams ps, const Geometry& g, int side, void* coef, float* bias_part,
+                        hipStream_t stream) {
+  const int np = xv_npad(g);
+  ps.x.side = side;
+  ps.x.gbuf = static_cast<char*>(coef);
+  ps.x.ldg = (long long)g.world * np * (long long)dtype_size(comp);
+  ps.x.plane_bytes = (long long)np * ps.x.ldg;
+  ps.bias_part = bias_part;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<decltype(tc)>), dim3((int)xv_sig_tiles(g)), dim3(dev::kXvThreads), 0,
+                       stream, ps);
+  });
 }
 }  // namespace
 
@@ -869,7 +914,7 @@ size_t xview_sigmoid_bias_part_bytes(const Geometry& g) { return xv_sig_tiles(g)
 void launch_xview_sigmoid_pos(DType in, const void* h, const float* inv, const Geometry& g, float* pos_cos,
                               hipStream_t stream) {
   NTXENT_CHECK(h && inv && pos_cos, "xview_sigmoid_pos: null buffer");
-  NTXENT_CHECK(in != DType::FP8 && g.world == 1, "xview_sigmoid_pos: fp32 | fp16 | bf16 rows of one rank");
+  NTXENT_CHECK(in != DType::FP8, "xview_sigmoid_pos: fp32 | fp16 | bf16 rows");
   const int n = g.rows / 2;
   dispatch_comp(in, [&](auto tin) {
     using Tin = decltype(tin);
@@ -885,13 +930,10 @@ void launch_xview_sigmoid_fwd(DType comp, const void* zq, const Geometry& g, flo
   dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, "xview_sigmoid_fwd");
   ps.pos_cos = pos_cos;
   ps.lpart = static_cast<double*>(scratch);
-  const int ntiles = (int)xv_sig_tiles(g);
-  dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, ps);
-  });
+  xv_sig_launch_fwd(comp, ps, stream);
   // the tiles' partials in a fixed order, over the n pairs
-  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, ps.lpart, ntiles,
-                     (double)(g.rows / 2), loss, nullptr);
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, ps.lpart,
+                     (int)xv_sig_tiles(g), (double)(g.rows / 2), loss, nullptr);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -900,25 +942,52 @@ void launch_xview_sigmoid_coef(DType comp, const void* zq, const Geometry& g, fl
   NTXENT_CHECK(zq && coef && zt && bias_part, "xview_sigmoid_coef: null buffer");
   dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, "xview_sigmoid_coef");
   ps.pos_cos = pos_cos;
-  const int np = xv_npad(g);
-  ps.x.gbuf = static_cast<char*>(coef);
-  ps.x.ldg = (long long)np * (long long)dtype_size(comp);
-  ps.x.plane_bytes = (long long)np * ps.x.ldg;
-  ps.bias_part = bias_part;
   xv_launch_zt(comp, zq, g, zt, stream);
-  dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<decltype(tc)>), dim3((int)xv_sig_tiles(g)), dim3(dev::kXvThreads), 0,
-                       stream, ps);
-  });
+  xv_sig_launch_coef(comp, ps, g, 0, coef, bias_part, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_sigmoid_bias_grad(const float* bias_part, const float* grad_out, float* dbias, const Geometry& g,
-                                    hipStream_t stream) {
-  NTXENT_CHECK(bias_part && grad_out && dbias, "xview_sigmoid_bias_grad: null buffer");
-  NTXENT_CHECK(g.world == 1, "xview_sigmoid_bias_grad: one rank only");
+                                    hipStream_t stream, double* share64) {
+  NTXENT_CHECK(bias_part && grad_out && (dbias != nullptr) != (share64 != nullptr),
+               "xview_sigmoid_bias_grad: null buffer (one of dbias and share64)");
+  // 2 N: the rows of the global batch (one GPU: 2 n)
   hipLaunchKernelGGL(dev::xview_sigmoid_bias_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, bias_part,
-                     (int)(4 * xv_sig_tiles(g)), grad_out, 2.0 * (double)(g.rows / 2), dbias);
+                     (int)(4 * xv_sig_tiles(g)), grad_out, (double)g.global_rows, dbias, share64);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+// rank g.rank of g.world
+void launch_xview_sigmoid_dist_fwd(DType comp, const void* zq_all, const Geometry& g, float bias, int q_lo, int q_hi,
+                                   int q_skip, double* lpart, hipStream_t stream, const float* pos_cos) {
+  NTXENT_CHECK(zq_all && lpart, "xview_sigmoid_dist_fwd: null buffer");
+  NTXENT_CHECK(0 <= q_lo && q_lo <= q_hi && q_hi <= g.world && q_skip < q_hi && (q_skip < 0 || q_skip >= q_lo),
+               "xview_sigmoid_dist_fwd: bad slot range");
+  dev::XvSigParams ps = xv_sig_params(comp, zq_all, g, bias, "xview_sigmoid_dist_fwd", false);
+  ps.x.q_lo = q_lo;
+  ps.x.nq = q_hi - q_lo - (q_skip >= 0 ? 1 : 0);
+  ps.x.q_skip = q_skip;
+  ps.pos_cos = pos_cos;
+  ps.lpart = lpart;
+  if (ps.x.nq == 0) return;
+  xv_sig_launch_fwd(comp, ps, stream);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_sigmoid_dist_loss(const double* lpart, const Geometry& g, double* share, hipStream_t stream) {
+  NTXENT_CHECK(lpart && share, "xview_sigmoid_dist_loss: null buffer");
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpart, (int)xv_sig_tiles(g),
+                     (double)(g.global_rows / 2), nullptr, share);
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_sigmoid_dist_coef(DType comp, const void* zq_all, const Geometry& g, float bias, int side, void* coef,
+                                    float* bias_part, hipStream_t stream, const float* pos_cos) {
+  NTXENT_CHECK(zq_all && coef && (side == 0 || side == 1), "xview_sigmoid_dist_coef: bad argument");
+  NTXENT_CHECK((side == 0) == (bias_part != nullptr), "xview_sigmoid_dist_coef: bias_part with side 0 and only there");
+  dev::XvSigParams ps = xv_sig_params(comp, zq_all, g, bias, "xview_sigmoid_dist_coef", false);
+  ps.pos_cos = pos_cos;
+  xv_sig_launch_coef(comp, ps, g, side, coef, bias_part, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 

@@ -549,6 +549,85 @@ at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, co
   return xview_backward_tail(h, inv, go, dz, coef, zt, g, stream);
 }
 
+// ---- distributed pairwise sigmoid loss: stage ops (parallel/sigmoid.py and parallel/emulate.py call
+// the same three) ----------------------------------------------------------------------------------
+// Side 0's forward tiles against the rank slots [q_lo, q_hi) except q_skip (-1: none) into the
+// caller's lpart (float64 [xview_sigmoid_dist_tiles]); every tile has its own place there. h, inv:
+// this rank's rows and prep's inv: a 16-bit plan whose slots include the own one takes the positives'
+// cosines from them (the own slot alone holds positives).
+void xview_sigmoid_dist_fwd(const at::Tensor& zq_all, const Plan& P, at::Tensor& lpart, const at::Tensor& h,
+                            const at::Tensor& inv, double bias, int q_lo, int q_hi, int q_skip) {
+  check_xview_dist(zq_all, P);
+  check_input(lpart, "lpart");
+  check_input(h, "h");
+  const Geometry& g = P.g;
+  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(g) && lpart.scalar_type() == at::kDouble,
+               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows]");
+  const at::DeviceGuard guard(zq_all.device());
+  const bool own = q_lo <= g.rank && g.rank < q_hi && q_skip != g.rank;
+  const at::Tensor pos = own ? sigmoid_pos_cos(h, inv, P.comp, g) : at::Tensor();
+  launch_xview_sigmoid_dist_fwd(P.comp, zq_all.data_ptr(), g, (float)bias, q_lo, q_hi, q_skip, lpart.data_ptr<double>(),
+                                cur_stream(zq_all), pos.defined() ? pos.data_ptr<float>() : nullptr);
+}
+
+// This rank's share of the loss, a 0-d float64 tensor (a SUM over the ranks, rounded to float32 once,
+// gives the loss).
+at::Tensor xview_sigmoid_dist_loss(const at::Tensor& lpart, const Plan& P) {
+  check_input(lpart, "lpart");
+  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(P.g) && lpart.scalar_type() == at::kDouble,
+               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
+  const at::DeviceGuard guard(lpart.device());
+  auto share = at::empty({}, opts(lpart, at::kDouble));
+  launch_xview_sigmoid_dist_loss(lpart.data_ptr<double>(), P.g, share.data_ptr<double>(), cur_stream(lpart));
+  return share;
+}
+
+// Rank-local backward from the gathered rows: the slots' transposes, then per side the coefficient
+// block (one buffer) and its dZ rows, then the normalisation backward with the global scale. Returns
+// (dh, shares): shares float64 [2] = this rank's shares of (dL/dtau, dL/dbias) times grad_out (an entry
+// not wanted is zero), undefined if neither is wanted; dh is bitwise the same either way.
+std::tuple<at::Tensor, at::Tensor> xview_sigmoid_dist_backward(const at::Tensor& h, const at::Tensor& zq_all,
+                                                               const at::Tensor& inv, const at::Tensor& grad_out,
+                                                               const Plan& P, double bias, bool want_tau,
+                                                               bool want_bias) {
+  check_input(h, "h");
+  check_xview_dist(zq_all, P);
+  const Geometry& g = P.g;
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat,
+               "xview_sigmoid_dist_backward: inv must be float32 [rows]");
+  const at::DeviceGuard guard(h.device());
+  const hipStream_t stream = cur_stream(h);
+  auto go = grad_scalar(grad_out);
+  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto coef = at::empty({(long)xview_coef_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto bias_part = at::empty({(long)(xview_sigmoid_bias_part_bytes(g) / 4)}, opts(h, at::kFloat));
+  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
+  launch_xview_dist_zt(P.comp, zq_all.data_ptr(), g, zt.data_ptr(), stream);
+  {
+    const at::Tensor pos = sigmoid_pos_cos(h, inv, P.comp, g);
+    for (int side = 0; side < 2; ++side) {
+      launch_xview_sigmoid_dist_coef(P.comp, zq_all.data_ptr(), g, (float)bias, side, coef.data_ptr(),
+                                     side == 0 ? bias_part.data_ptr<float>() : nullptr, stream,
+                                     pos.defined() ? pos.data_ptr<float>() : nullptr);
+      launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), stream);
+    }
+  }
+  at::Tensor dot, shares;
+  auto dh = xview_backward_tail(h, inv, go, dz, coef, zt, g, stream, &dot);
+  if (want_tau || want_bias) {
+    shares = at::zeros({2}, opts(h, at::kDouble));
+    if (want_tau)
+      launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream, shares.data_ptr<double>());
+    if (want_bias)
+      launch_xview_sigmoid_bias_grad(bias_part.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream,
+                                     shares.data_ptr<double>() + 1);
+  }
+  return {dh, shares};
+}
+
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {
   check_input(zq, "zq");
   const at::DeviceGuard guard(zq.device());
@@ -1575,6 +1654,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("plan"));
   m.def("xview_dist_backward", &xview_dist_backward, py::arg("h"), py::arg("zq_all"), py::arg("inv"),
         py::arg("lse2_all"), py::arg("cpos"), py::arg("grad_out"), py::arg("plan"));
+  m.def("xview_sigmoid_dist_tiles", [](const Plan& P) { return (long)(xview_sigmoid_scratch_bytes(P.g) / 8); });
+  m.def("xview_sigmoid_dist_fwd", &xview_sigmoid_dist_fwd, py::arg("zq_all"), py::arg("plan"), py::arg("lpart"),
+        py::arg("h"), py::arg("inv"), py::arg("bias"), py::arg("q_lo"), py::arg("q_hi"), py::arg("q_skip") = -1);
+  m.def("xview_sigmoid_dist_loss", &xview_sigmoid_dist_loss, py::arg("lpart"), py::arg("plan"));
+  m.def("xview_sigmoid_dist_backward", &xview_sigmoid_dist_backward, py::arg("h"), py::arg("zq_all"), py::arg("inv"),
+        py::arg("grad_out"), py::arg("plan"), py::arg("bias"), py::arg("want_tau"), py::arg("want_bias"));
   m.def("tile_list_uploads", []() { return g_tile_uploads.load(); });
   m.def("set_small_path", &ntxent::set_small_path, py::arg("on"));
   m.def("small_path_enabled", &ntxent::small_path_enabled);

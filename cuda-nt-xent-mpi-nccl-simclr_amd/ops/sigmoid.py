@@ -95,7 +95,7 @@ def sigmoid_loss(h: torch.Tensor, temperature=0.1, bias=-10.0, *, z2: Optional[t
         fp16: these kernels have no fp8 operands.
       use_mixed_precision: fp32 inputs are computed in fp16 (fp32 accumulate) if True.
 
-    One GPU; there is no distributed form.
+    One GPU; the data-parallel form is ``parallel.sigmoid.dist_sigmoid_loss``.
     """
     h = _stack_views(h, z2)
     if _use_reference(h):

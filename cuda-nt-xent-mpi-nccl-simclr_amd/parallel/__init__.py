@@ -5,5 +5,7 @@ from .commstats import use_compute_stream  # noqa: F401
 from .distributed import DistNTXentFunction, cpu_dist_ntxent_loss, dist_ntxent_loss  # noqa: F401
 from .infonce import (DistInfoNCEFunction, DistInfoNCELoss, cpu_dist_info_nce_loss,  # noqa: F401
                       dist_info_nce_loss)
+from .sigmoid import (DistSigmoidFunction, DistSigmoidLoss, cpu_dist_sigmoid_loss,  # noqa: F401
+                      dist_sigmoid_loss)
 from .ring import RingNTXentFunction, ring_ntxent_loss  # noqa: F401
 from .symmetric import SymNTXentFunction, cpu_sym_ntxent_loss, sym_jobs, sym_ntxent_loss  # noqa: F401

@@ -96,6 +96,44 @@ def emulated_xview_forward_backward(shards: Sequence[torch.Tensor], temperature:
     return loss.float(), [C.xview_dist_backward(hs[r], zq_all, preps[r][1], lse2_all, cposs[r], go, plans[r]) for r in range(W)]
 
 
+def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperature: float, bias: float, *,
+                                      compute: str = "auto", grad_out: float = 1.0, want_tau: bool = True,
+                                      want_bias: bool = True):
+    """Distributed pairwise sigmoid loss (:mod:`parallel.sigmoid`) for W virtual ranks on one device:
+    ``(loss, grads, dtau, dbias)`` for shards h_r = [a_r; b_r]: the loss of the global batch in pair
+    order, per-rank dL/dh_r, and the two scalar gradients (0-d fp32), all times ``grad_out``. Every
+    rank's prep writes its slot of the shared ``zq_all``; the fp64 shares of the loss and of the
+    scalar gradients are summed as the all-reduces would and rounded to fp32 once. A scalar gradient
+    that is not wanted is None (with neither the backward stage returns no shares, as a backward
+    that does not communicate)."""
+    from .infonce import _CDT, xview_compute
+    from .sigmoid import sigmoid_stage_forward
+
+    C = _ext.load()
+    W = len(shards)
+    R, d = shards[0].shape
+    dev = shards[0].device
+    comp = xview_compute(shards[0].dtype, False, compute)
+    plans = [C.get_plan(R, d, W, r, float(temperature), comp, dev.index) for r in range(W)]
+    Rpad = plans[0].rows_pad
+    hs = [x.contiguous() for x in shards]
+    zq_all = torch.empty((W * Rpad, plans[0].ld_k), dtype=_CDT[comp], device=dev)
+    preps = [C.prep(hs[r], plans[r], zq_all[r * Rpad:(r + 1) * Rpad], None) for r in range(W)]  # "all-gather"
+    loss = torch.zeros((), dtype=torch.float64, device=dev)
+    for r in range(W):
+        loss = loss + sigmoid_stage_forward(C, plans[r], zq_all, hs[r], preps[r][1], float(bias))  # "all-reduce"
+    go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
+    grads, scalars = [], torch.zeros((2,), dtype=torch.float64, device=dev)
+    for r in range(W):
+        dh, shares = C.xview_sigmoid_dist_backward(hs[r], zq_all, preps[r][1], go, plans[r], float(bias),
+                                                   bool(want_tau), bool(want_bias))
+        grads.append(dh)
+        if shares is not None:
+            scalars = scalars + shares  # "all-reduce" (fp64 shares)
+    scalars = scalars.float()
+    return loss.float(), grads, scalars[0] if want_tau else None, scalars[1] if want_bias else None
+
+
 def emulated_ring_forward_backward(shards: Sequence[torch.Tensor], temperature: float, *, compute: str = "auto",
                                    grad_out: float = 1.0) -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """The ring-negatives stage ops (:mod:`parallel.ring`) for W virtual ranks on one device:

@@ -1,0 +1,238 @@
+"""Pairwise sigmoid loss (the SigLIP form) with the negatives of the whole data-parallel batch.
+
+Rank r of W holds ``h_r = [a_r; b_r]`` (n rows per tower). With ``[a; b]`` the global batch in pair
+order (``reference.global_pair_order``), N = W n pairs and ``x_ij = a_i . b_j / tau + bias``::
+
+    loss = (1 / N) sum_{i,j < N} softplus(-s_ij x_ij),    s_ii = +1, s_ij = -1 otherwise
+
+is ``reference.sigmoid_loss`` of the global batch, identical on every rank. ``dh`` is its exact
+gradient w.r.t. this rank's rows (the convention of ``dist_info_nce_loss``: a trainer under DDP
+multiplies by the world size); dL/dtau and dL/dbias are the exact gradients of the returned global
+loss, all-reduced and identical on every rank. Temperature and bias must be the same numbers on
+every rank (not checked).
+
+* forward: prep -> all-gather of the unit rows ``zq`` (compute dtype) into ``zq_all [W Rpad][ld_k]``
+  while the tiles of the own column block run -> the other blocks -> the rank's fp64 share of the
+  loss -> all-reduce (8 B). Only ``a_r`` against ``b`` of all ranks is computed, an n x N block:
+  every global pair is a binary term of its own and is computed exactly once somewhere, half the
+  similarity FLOPs of ``dist_info_nce_loss``'s forward, and no normaliser crosses ranks.
+* backward: rank-local from the saved ``h``, ``zq_all`` and ``inv``. Per side the coefficient block
+  ``C = 2 G`` (``G = sigmoid(x)``, on the positives ``-sigmoid(-x)``) and its dZ rows; side 1 swaps
+  the operand roles and so gives the rows of ``C^T`` directly. If a scalar gradient is wanted, one
+  all-reduce of the two fp64 shares (16 B) ends it; otherwise the backward does not communicate.
+  ``dh`` is bitwise the same either way.
+
+Bytes across ranks per step and rank: the gather of ``(W - 1) Rpad ld_k`` elements of the compute
+dtype, 8 B for the loss, 16 B for the scalar gradients.
+
+``csrc/kernels/xview_kernels.hip`` (the ``xview_sigmoid_*`` kernels); the stage ops are shared with
+``parallel/emulate.emulated_sigmoid_forward_backward``.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.distributed as dist
+
+from ..ops import _ext, reference
+from ..ops.ntxent import _stack_views, _tau_grad, _tau_like, _TemperatureModule, temperature_wants_grad
+from ..ops.sigmoid import _host_values, sigmoid_loss
+from .commstats import span
+from .distributed import _all_gather_into, _world
+from .infonce import _CDT, _gather, xview_compute
+
+
+def sigmoid_stage_forward(C, plan, zq_all: torch.Tensor, h: torch.Tensor, inv: torch.Tensor, bias: float, wait=None):
+    """One rank's forward stage ops over the gathered rows: the own column block, ``wait()`` (the rows
+    of the other ranks have arrived), the other blocks, the fixed-order sum. Every tile writes its own
+    place of one array, so the split over two launches does not change the sum. Returns the rank's
+    share of the loss, a 0-d float64 tensor."""
+    W, r = plan.world, plan.rank
+    lpart = torch.empty((C.xview_sigmoid_dist_tiles(plan),), dtype=torch.float64, device=zq_all.device)
+    C.xview_sigmoid_dist_fwd(zq_all, plan, lpart, h, inv, bias, r, r + 1)
+    if wait is not None:
+        wait()
+    C.xview_sigmoid_dist_fwd(zq_all, plan, lpart, h, inv, bias, 0, W, r)
+    return C.xview_sigmoid_dist_loss(lpart, plan)
+
+
+class DistSigmoidFunction(torch.autograd.Function):
+    """``tau`` / ``bias_t`` are None, or the one-element temperature / bias tensors whose gradients
+    are wanted (``ops.sigmoid.SigmoidFunction``'s convention)."""
+
+    @staticmethod
+    def forward(ctx, h: torch.Tensor, temperature: float, bias: float, compute: str, group, overlap: bool,
+                tau: Optional[torch.Tensor] = None, bias_t: Optional[torch.Tensor] = None):
+        C = _ext.load()
+        W, r = _world(group)
+        h = h.contiguous()
+        R, d = h.shape
+        plan = C.get_plan(R, d, W, r, float(temperature), compute, h.device.index)
+        Rpad = plan.rows_pad
+        # prep writes straight into this rank's slot: the gather runs in place
+        zq_all = torch.empty((W * Rpad, plan.ld_k), dtype=_CDT[compute], device=h.device)
+        zq = zq_all[r * Rpad:(r + 1) * Rpad]
+        _, inv, _, _ = C.prep(h, plan, zq, None)
+        work = _all_gather_into(zq_all, zq, group, async_op=True) if W > 1 else None
+
+        def wait():
+            if work is not None:
+                with span("fwd_rows"):
+                    work.wait()
+
+        if not overlap:
+            wait()
+        share = sigmoid_stage_forward(C, plan, zq_all, h, inv, float(bias), wait if overlap else None)
+        if W > 1:
+            with span("sigmoid_loss"):
+                dist.all_reduce(share, op=dist.ReduceOp.SUM, group=group)  # fp64 shares (8 B)
+        ctx.plan, ctx.bias, ctx.group = plan, float(bias), group
+        ctx.tau = _tau_like(tau)
+        ctx.bias_like = _tau_like(bias_t)
+        ctx.save_for_backward(h, zq_all, inv)
+        return share.float()  # the one rounding to fp32, as the one-GPU loss has
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        h, zq_all, inv = ctx.saved_tensors
+        want_tau = ctx.tau is not None and ctx.needs_input_grad[6]
+        want_bias = ctx.bias_like is not None and ctx.needs_input_grad[7]
+        dh, shares = _ext.load().xview_sigmoid_dist_backward(h, zq_all, inv, grad_out.reshape(1), ctx.plan, ctx.bias,
+                                                             want_tau, want_bias)
+        dtau = dbias = None
+        if want_tau or want_bias:
+            if ctx.plan.world > 1:
+                with span("sigmoid_scalars"):
+                    dist.all_reduce(shares, op=dist.ReduceOp.SUM, group=ctx.group)  # fp64 shares (16 B)
+            both = shares.float()  # one rounding to fp32 each
+            dtau = _tau_grad(both[0], ctx.tau) if want_tau else None
+            dbias = _tau_grad(both[1], ctx.bias_like) if want_bias else None
+        return dh, None, None, None, None, None, dtau, dbias
+
+
+def dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, *, z2: Optional[torch.Tensor] = None,
+                      group=None, compute: str = "auto", use_mixed_precision: bool = False,
+                      overlap: bool = True) -> torch.Tensor:
+    """Global pairwise sigmoid loss over the data-parallel group; ``h_local = [a_r; b_r]`` on each
+    rank (or ``h_local = a_r, z2 = b_r``), the same n and d on every rank.
+
+    temperature, bias: floats or one-element tensors, the same numbers on every rank (not checked). A
+      tensor that requires grad (or has a ``grad_fn``) receives the gradient of the returned global
+      loss, all-reduced: identical on every rank, in the tensor's own dtype, shape and device. Loss
+      and dh are bitwise those of the same floats.
+    compute: ``auto|fp32|fp16|bf16|fp8`` as for ``sigmoid_loss`` (``fp8`` computes in fp16).
+    overlap: launch the tiles of the own column block before the row gather is waited for (the same
+      bits either way).
+    Without a process group, or in a group of one, this is ``sigmoid_loss``. CPU tensors take
+    ``cpu_dist_sigmoid_loss``.
+    """
+    W, _ = _world(group)
+    if W == 1:
+        return sigmoid_loss(h_local, temperature, bias, z2=z2, compute=compute, use_mixed_precision=use_mixed_precision)
+    h = _stack_views(h_local, z2)
+    if not h.is_cuda:
+        return cpu_dist_sigmoid_loss(h, temperature, bias, group=group)
+    comp = xview_compute(h.dtype, use_mixed_precision, compute)
+    tv, bv = _host_values(temperature, bias)
+    tau = temperature if temperature_wants_grad(temperature) else None
+    bias_t = bias if temperature_wants_grad(bias) else None
+    return DistSigmoidFunction.apply(h, tv, bv, comp, group, bool(overlap), tau, bias_t)
+
+
+class DistSigmoidLoss(_TemperatureModule):
+    """``nn.Module`` front end: ``DistSigmoidLoss(temperature, bias)(z1, z2)`` or ``(h)`` on every rank.
+
+    ``learnable_temperature`` / ``temperature_bounds`` / ``learnable_bias`` as ``SigmoidLoss``. The
+    parameters' gradients are those of the global loss, the same on every rank: they need no further
+    reduction (and, under a trainer that scales the loss by the world size for DDP's mean, are
+    scaled with it)."""
+
+    def __init__(self, temperature: float = 0.1, bias: float = -10.0, compute: str = "auto", group=None,
+                 use_mixed_precision: bool = False, overlap: bool = True, learnable_temperature: bool = False,
+                 temperature_bounds=(0.01, 1.0), learnable_bias: bool = False):
+        super().__init__()
+        self.compute = compute
+        self.group = group
+        self.use_mixed_precision = use_mixed_precision
+        self.overlap = overlap
+        self._init_temperature(temperature, learnable_temperature, temperature_bounds)
+        self.learnable_bias = bool(learnable_bias)
+        self.initial_bias = float(bias)
+        if self.learnable_bias:
+            self.bias = torch.nn.Parameter(torch.tensor(float(bias), dtype=torch.float32))
+        else:
+            self.bias = float(bias)
+
+    def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return dist_sigmoid_loss(z1, self.current_temperature(), self.bias, z2=z2, group=self.group,
+                                 compute=self.compute, use_mixed_precision=self.use_mixed_precision,
+                                 overlap=self.overlap)
+
+    def extra_repr(self) -> str:
+        return (f"temperature={self.temperature}, bias={self.initial_bias}, compute={self.compute}"
+                + self._temperature_repr() + (", learnable_bias=True" if self.learnable_bias else ""))
+
+
+# ---------------------------------------------------------------------------------------
+# CPU / gloo path: the same algorithm (gather unit rows, side 0's n x N block forward, rank-local
+# backward from both sides, one all-reduce of the two scalar shares) written with torch ops.
+# ---------------------------------------------------------------------------------------
+class _CpuDistSigmoidFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, temperature, bias, group, tau, bias_t):
+        W, r = _world(group)
+        n = h.shape[0] // 2
+        z, inv = reference.normalize(h)
+        zs = _gather(z, W, group)
+        # towers[v]: view v of every rank, rank slots in order (the columns of side 1 - v)
+        towers = [torch.cat([q[:n] for q in zs], 0), torch.cat([q[n:] for q in zs], 0)]
+        x = z[:n] @ towers[1].t() / temperature + bias  # side 0 only: every global pair once
+        s = -torch.ones_like(x)
+        s[torch.arange(n), torch.arange(n) + r * n] = 1.0
+        loss = torch.nn.functional.softplus(-s * x).sum() / (W * n)
+        if W > 1:
+            dist.all_reduce(loss, group=group)
+        ctx.save_for_backward(z, inv, *towers)
+        ctx.meta = (temperature, bias, W, r, group, _tau_like(tau), _tau_like(bias_t))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, inv, t0, t1 = ctx.saved_tensors
+        temperature, bias, W, r, group, tau_like, bias_like = ctx.meta
+        n = z.shape[0] // 2
+        N = W * n
+        ar = torch.arange(n)
+        towers = (t0, t1)
+        dz, G0 = [], None
+        for v in (0, 1):  # side 1: the same formula with the roles swapped gives the rows of G^T
+            cos = z[v * n:(v + 1) * n] @ towers[1 - v].t()
+            x = cos / temperature + bias
+            G = torch.sigmoid(x)
+            G[ar, ar + r * n] = -torch.sigmoid(-x[ar, ar + r * n])
+            dz.append(G @ towers[1 - v])
+            if v == 0:
+                G0, cos0 = G, cos
+        dz = torch.cat(dz, 0) * (g / (N * temperature))
+        dot = (z * dz).sum(1, keepdim=True)
+        dh = inv.unsqueeze(1) * (dz - z * dot)
+        want_tau = tau_like is not None and ctx.needs_input_grad[4]
+        want_bias = bias_like is not None and ctx.needs_input_grad[5]
+        dtau = dbias = None
+        if want_tau or want_bias:  # each pair counts once: side 0's block
+            shares = torch.stack([-(G0 * cos0).sum() / (N * temperature * temperature), G0.sum() / N]).double() * g.double()
+            if W > 1:
+                dist.all_reduce(shares, group=group)
+            dtau = _tau_grad(shares[0], tau_like) if want_tau else None
+            dbias = _tau_grad(shares[1], bias_like) if want_bias else None
+        return dh, None, None, None, dtau, dbias
+
+
+def cpu_dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, group=None) -> torch.Tensor:
+    """The distributed algorithm in torch ops over gloo, for CPU tensors (any float dtype)."""
+    h = _stack_views(h_local, None)
+    tv, bv = _host_values(temperature, bias)
+    tau = temperature if temperature_wants_grad(temperature) else None
+    bias_t = bias if temperature_wants_grad(bias) else None
+    return _CpuDistSigmoidFn.apply(h, tv, bv, group, tau, bias_t)

@@ -18,6 +18,17 @@ The document records the median, mean, min and max per arm in ms, the ratios, th
 torch.cuda.max_memory_allocated deltas of one forward + backward of ``op`` and ``eager``, and how
 far the two losses are apart. No speed threshold: the op shares InfoNCE's plain one-tile-per-workgroup
 GEMMs and may not beat eager.
+
+  python tools/sigmoid_cost.py --world W [--out profiles/sigmoid_dist/sigmoid_cost_wW.json]
+
+times one virtual rank of the distributed form (``ntxent_amd.parallel.dist_sigmoid_loss``) instead: its
+forward + backward stage ops, both scalar gradients wanted, against gathered rows filled on the
+device (no collective is timed), B = 4096 per view and rank, d = 512 and 2048, fp16. Three arms in the
+same run: the op; the eager PyTorch expression of the same per-rank work in the same arithmetic
+(fp16 unit rows and matmuls, fp32 elementwise: a_r B_all^T forward, both sides through autograd);
+and one rank of ``dist_info_nce_loss`` on the same rows. ``--memory`` records instead the
+torch.cuda.max_memory_allocated delta of one emulated rank's step at W = 2, n = 1024, d = 512, fp16,
+for both losses.
 """
 from __future__ import annotations
 
@@ -70,9 +81,144 @@ def peak_delta(fn) -> int:
     return torch.cuda.max_memory_allocated() - base
 
 
+WORLD_SHAPES = [("d512", 4096, 512), ("d2048", 4096, 2048)]
+
+
+def _rank_setup(C, W, batch, dim, dev, dtype=torch.float16, comp="fp16", tau=TAU):
+    """Plans, this process's virtual ranks' rows and zq_all with every slot filled by its rank's prep."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    plans = [C.get_plan(2 * batch, dim, W, q, tau, comp, dev.index) for q in range(W)]
+    Rpad = plans[0].rows_pad
+    zq_all = torch.empty((W * Rpad, plans[0].ld_k), dtype=dtype, device=dev)
+    hs = []
+    for q in range(W):
+        h1 = torch.randn(batch, dim, generator=g, device=dev)
+        s = 1.5 * torch.rand(batch, 1, generator=g, device=dev)
+        hs.append(torch.cat([h1, s * h1 + torch.randn(batch, dim, generator=g, device=dev)], 0).to(dtype))
+        C.prep(hs[q], plans[q], zq_all[q * Rpad:(q + 1) * Rpad], None)
+    return plans, hs, zq_all, Rpad
+
+
+def _rank_steps(C, plans, hs, zq_all, Rpad, r, dev):
+    """(sigmoid rank step, InfoNCE rank step, sigmoid forward alone) of virtual rank r as closures."""
+    from ntxent_amd.parallel.infonce import xview_stage_forward
+    from ntxent_amd.parallel.sigmoid import sigmoid_stage_forward
+
+    W = len(plans)
+    plan, h = plans[r], hs[r]
+    mine = zq_all[r * Rpad:(r + 1) * Rpad]
+    go = torch.ones(1, dtype=torch.float32, device=dev)
+    lse2_all = torch.empty((W * Rpad,), dtype=torch.float32, device=dev)
+    for q in range(W):  # the other ranks' LSE: a device-filled "gather"
+        xview_stage_forward(C, plans[q], zq_all, torch.empty((h.shape[0],), dtype=torch.float32, device=dev), lse2_all)
+
+    def op_forward():
+        _, inv, _, _ = C.prep(h, plan, mine, None)
+        return inv, sigmoid_stage_forward(C, plan, zq_all, h, inv, BIAS)
+
+    def op():
+        inv, _ = op_forward()
+        return C.xview_sigmoid_dist_backward(h, zq_all, inv, go, plan, BIAS, True, True)
+
+    def info_nce():
+        _, inv, ypos, _ = C.prep(h, plan, mine, None)
+        _, cpos = xview_stage_forward(C, plan, zq_all, ypos, lse2_all)
+        return C.xview_dist_backward(h, zq_all, inv, lse2_all, cpos, go, plan)
+
+    return op, info_nce, op_forward
+
+
+def world_cost(args, dev):
+    from ntxent_amd.ops import _ext
+
+    C = _ext.load()
+    W, r = args.world, args.world // 2
+    doc = {"device": torch.cuda.get_device_name(0), "dtype": "fp16", "temperature": TAU, "bias": BIAS,
+           "iters": args.iters, "rounds": args.rounds, "world": W, "rank": r, "shapes": {}}
+    for name, batch, dim in WORLD_SHAPES:
+        plans, hs, zq_all, Rpad = _rank_setup(C, W, batch, dim, dev)
+        op, info_nce, op_forward = _rank_steps(C, plans, hs, zq_all, Rpad, r, dev)
+        zf = [F.normalize(x.float(), dim=1).half() for x in hs]  # the other ranks' unit rows: constants
+        x = hs[r].clone().requires_grad_(True)
+        N = W * batch
+        sign = -torch.ones(batch, N, device=dev)
+        sign[torch.arange(batch), torch.arange(batch) + r * batch] = 1.0
+
+        a_oth = torch.cat([zf[q][:batch] for q in range(W) if q != r], 0)
+
+        def eager():
+            # the rank's forward block a_r B_all^T (b_r live in its own slot), and for the rest of b_r's
+            # gradient its pairs with the a of the other ranks (all negatives): every pair once
+            x.grad = None
+            z = F.normalize(x.float(), dim=1).half()
+            a, b = z[:batch], z[batch:]
+            b_all = torch.cat([b if q == r else zf[q][batch:] for q in range(W)], 0)
+            fwd = F.softplus(-sign * ((a @ b_all.t()).float() / TAU + BIAS)).sum() / N
+            other = F.softplus((b @ a_oth.t()).float() / TAU + BIAS).sum() / N
+            (fwd + other).backward()
+            return fwd
+
+        arms = {"op": op, "eager": eager, "info_nce": info_nce, "op_forward": op_forward}
+        for fn in arms.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in arms}
+        for _ in range(args.rounds):
+            for k, fn in arms.items():
+                ms[k] += time_arm(fn, args.iters)
+        x.grad = None
+        mem = {k: peak_delta(arms[k]) for k in ("op", "eager", "info_nce")}
+        rec = {k: summary(v) for k, v in ms.items()}
+        rec.update(batch=batch, dim=dim, rows=2 * batch, world=W,
+                   op_over_eager=rec["op"]["median_ms"] / rec["eager"]["median_ms"],
+                   op_over_info_nce=rec["op"]["median_ms"] / rec["info_nce"]["median_ms"],
+                   op_backward_median_ms=rec["op"]["median_ms"] - rec["op_forward"]["median_ms"],
+                   peak_bytes_op=mem["op"], peak_bytes_eager=mem["eager"], peak_bytes_info_nce=mem["info_nce"],
+                   gathered_bytes=zq_all.numel() * 2, share_op=float(op_forward()[1]), share_eager=float(eager().detach()))
+        doc["shapes"][name] = rec
+        print(f"W={W} {name}: op {rec['op']['median_ms']:.4f} ms (forward {rec['op_forward']['median_ms']:.4f}), eager "
+              f"{rec['eager']['median_ms']:.4f} ms, info_nce rank {rec['info_nce']['median_ms']:.4f} ms (medians); op/eager "
+              f"{rec['op_over_eager']:.3f}, op/info_nce {rec['op_over_info_nce']:.3f}; peak MiB op {mem['op'] / 2**20:.1f}, "
+              f"eager {mem['eager'] / 2**20:.1f}, info_nce {mem['info_nce'] / 2**20:.1f} (beside "
+              f"{rec['gathered_bytes'] / 2**20:.1f} gathered); loss share op {rec['share_op']:.6f} eager "
+              f"{rec['share_eager']:.6f}", flush=True)
+        del zq_all, zf, hs, plans, op, info_nce, op_forward, a_oth, sign
+        torch.cuda.empty_cache()
+    return doc
+
+
+def memory_record(dev):
+    """torch.cuda.max_memory_allocated delta of one emulated rank's step (prep into its slot, forward,
+    backward) at W = 2, n = 1024, d = 512, fp16, beside zq_all: the sigmoid loss and InfoNCE."""
+    from ntxent_amd.ops import _ext
+
+    C = _ext.load()
+    plans, hs, zq_all, Rpad = _rank_setup(C, 2, 1024, 512, dev)
+    op, info_nce, _ = _rank_steps(C, plans, hs, zq_all, Rpad, 1, dev)
+    for fn in (op, info_nce):
+        fn()
+    doc = {"world": 2, "n": 1024, "dim": 512, "dtype": "fp16", "peak_bytes_sigmoid": peak_delta(op),
+           "peak_bytes_info_nce": peak_delta(info_nce), "gathered_bytes": zq_all.numel() * 2}
+    print(f"one emulated rank's step, W=2 n=1024 d=512 fp16: peak bytes sigmoid {doc['peak_bytes_sigmoid']}, "
+          f"info_nce {doc['peak_bytes_info_nce']} (beside {doc['gathered_bytes']} gathered)")
+    return doc
+
+
+def _write(doc, out):
+    out = Path(out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(doc, indent=1) + "\n")
+    print(f"wrote {out}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "sigmoid" / "sigmoid_cost.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/sigmoid/sigmoid_cost.json (profiles/sigmoid_dist/"
+                    "sigmoid_cost_wW.json with --world, memory.json with --memory)")
+    ap.add_argument("--world", type=int, default=1,
+                    help="W > 1: one virtual rank of the distributed form against device-filled gathered rows")
+    ap.add_argument("--memory", action="store_true", help="record one emulated rank's peak memory (W = 2) instead")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=5)
@@ -82,6 +228,12 @@ def main(argv=None):
     import ntxent_amd
 
     dev = torch.device("cuda", 0)
+    if args.memory or args.world > 1:
+        name = "memory.json" if args.memory else f"sigmoid_cost_w{args.world}.json"
+        _write(memory_record(dev) if args.memory else world_cost(args, dev),
+               args.out or ROOT / "profiles" / "sigmoid_dist" / name)
+        return
+    args.out = args.out or str(ROOT / "profiles" / "sigmoid" / "sigmoid_cost.json")
     doc = {"device": torch.cuda.get_device_name(0), "dtype": "bf16", "temperature": TAU, "bias": BIAS,
            "iters": args.iters, "rounds": args.rounds, "shapes": {}}
     for name, batch, dim in SHAPES:

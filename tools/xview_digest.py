@@ -9,6 +9,9 @@ with a CPU torch.Generator, in a fixed order:
   info_nce   loss, dh, dL/dtau of ``info_nce_loss`` (tau = 0.07 as a tensor that requires grad)
   pos_rank   rank, pos_cos, hard_neg_cos of ``positive_rank``
   xview_dist loss and every rank's dh of ``emulated_xview_forward_backward``
+  sigmoid    loss, dh, dL/dtau, dL/dbias of ``sigmoid_loss`` (tau = 0.1, bias = -10 as tensors that require grad)
+  sigmoid_dist loss, dL/dtau, dL/dbias and every rank's dh of ``emulated_sigmoid_forward_backward``
+             (a build without the distributed sigmoid loss prints none of these lines)
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ ONE_GPU = [(37, 40), (129, 160), (384, 256), (1024, 512)]  # (N pairs, d)
 COMPUTES = ["fp32", "fp16", "bf16"]
 DIST = [(2, 37, 40, "fp32"), (3, 129, 160, "fp32"), (3, 129, 160, "fp16"), (2, 200, 100, "bf16"), (8, 37, 40, "fp16")]
 TAU = 0.07
+SIG_TAU, SIG_BIAS = 0.1, -10.0
 
 
 def digest(t: torch.Tensor) -> str:
@@ -60,6 +64,24 @@ def main():
         shards = [rows(n, d, 1000 * n + d + 101 * r).to(dev) for r in range(W)]
         loss, grads = emulated_xview_forward_backward(shards, TAU, compute=comp, grad_out=0.7)
         print(f"xview_dist W={W} n={n} d={d} {comp}: loss {digest(loss)} " +
+              " ".join(f"dh{r} {digest(g)}" for r, g in enumerate(grads)))
+    for n, d in ONE_GPU:
+        h = rows(n, d, 1000 * n + d).to(dev)
+        for comp in COMPUTES:
+            x = h.clone().requires_grad_(True)
+            tau = torch.tensor(SIG_TAU, device=dev, requires_grad=True)
+            bias = torch.tensor(SIG_BIAS, device=dev, requires_grad=True)
+            loss = ntxent_amd.sigmoid_loss(x, tau, bias, compute=comp)
+            dh, dtau, dbias = torch.autograd.grad(loss, (x, tau, bias))
+            print(f"sigmoid N={n} d={d} {comp}: loss {digest(loss)} dh {digest(dh)} dtau {digest(dtau)} dbias {digest(dbias)}")
+    try:
+        from ntxent_amd.parallel.emulate import emulated_sigmoid_forward_backward
+    except ImportError:
+        emulated_sigmoid_forward_backward = None
+    for W, n, d, comp in DIST if emulated_sigmoid_forward_backward else []:
+        shards = [rows(n, d, 1000 * n + d + 101 * r).to(dev) for r in range(W)]
+        loss, grads, dtau, dbias = emulated_sigmoid_forward_backward(shards, SIG_TAU, SIG_BIAS, compute=comp, grad_out=0.7)
+        print(f"sigmoid_dist W={W} n={n} d={d} {comp}: loss {digest(loss)} dtau {digest(dtau)} dbias {digest(dbias)} " +
               " ".join(f"dh{r} {digest(g)}" for r, g in enumerate(grads)))
     torch.cuda.synchronize()
 
