@@ -549,6 +549,39 @@ void launch_xview_sigmoid_dist_loss(const double* lpart, const Geometry& g, doub
 void launch_xview_sigmoid_dist_coef(DType comp, const void* zq_all, const Geometry& g, float bias, int side, void* coef,
                                     float* bias_part, hipStream_t stream, const float* pos_cos = nullptr);
 
+// Block form of the same, for an exchange that hands a rank ONE other rank's rows at a time (the ring):
+// zq [Rpad][ld_k] is this rank's own slot, rows_q a buffer of the same shape that holds rank q's rows
+// (q == g.rank: zq itself). q is the slot's identity (own block, positives, output place), not a
+// buffer index. A stage reads up to local row n + n_pad of either buffer: pass whole slots. No buffer
+// below has a size that depends on g.world, except lpart and bias_part (nT * W * nT entries).
+//   launch_xview_sigmoid_block_fwd : the nT x nT tiles of a_r against b_q; tile (I, Jl) writes
+//     lpart[(I * W + q) * nT + Jl], the gather launch's place. After all W blocks (any order)
+//     launch_xview_sigmoid_dist_loss gives the share, bitwise the gather path's. pos_cos is taken for
+//     q == g.rank only.
+//   launch_xview_sigmoid_block_coef: ONE side of the block, C = 2 G as planes [planes][n_pad][n_pad]
+//     (xview_block_coef_bytes; ldg = n_pad elements; planes as launch_xview_coef; exact zeros outside
+//     the valid rows and columns). Side 1 swaps the operand roles: rows b_r against a_q, the rows of
+//     this block of C^T. bias_part with side 0 and only there, at ((I * W + q) * nT + Jl) * 4 + wave,
+//     the gather launch's place: launch_xview_sigmoid_bias_grad after all W blocks is bitwise the
+//     gather path's share.
+//   launch_xview_block_zt : zt [2][En][n_pad] (xview_block_zt_bytes): both views of rows_q transposed,
+//     zero padded by index.
+//   launch_xview_block_dz : rows [side * n, side * n + n) of the fp32 slab dz [Rpad][dim_n], K = n_pad
+//     per plane (the residual plane, the rescale, the hi plane). accumulate false: stored (the first
+//     block; the slab needs no memset); true: dz = dz + product with plain loads and stores. One
+//     workgroup owns an element per launch and the launches are stream-ordered: deterministic in the
+//     order of the blocks, no atomics.
+size_t xview_block_coef_bytes(DType comp, const Geometry& g);
+size_t xview_block_zt_bytes(DType comp, const Geometry& g);
+void launch_xview_sigmoid_block_fwd(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias, int q,
+                                    double* lpart, hipStream_t stream, const float* pos_cos = nullptr);
+void launch_xview_sigmoid_block_coef(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
+                                     int q, int side, void* coef, float* bias_part, hipStream_t stream,
+                                     const float* pos_cos = nullptr);
+void launch_xview_block_zt(DType comp, const void* rows_q, const Geometry& g, void* zt, hipStream_t stream);
+void launch_xview_block_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
+                           bool accumulate, hipStream_t stream);
+
 // ---- distributed cross-view InfoNCE: rank g.rank of g.world ranks ---------------------------------
 // The global-batch form of the loss above. Every rank holds n = R/2 pairs; the global batch in pair
 // order is [a_0; ..; a_{W-1}; b_0; ..; b_{W-1}] (N = W n pairs). zq_all [W * Rpad][ld_k] holds every

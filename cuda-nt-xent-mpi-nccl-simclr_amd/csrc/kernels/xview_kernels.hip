@@ -59,6 +59,9 @@
 // the forward runs side 0's n x W n block alone (every global pair is computed once, on the rank
 // that holds its row a_i), the coefficient pass one side at a time as xview_side_coef_kernel; one
 // GPU is W = 1, side 0 of both, with the in-place transpose in place of side 1.
+// The block form of both epilogues (kBlock) and of the dZ product (kAccum) serves the ring exchange:
+// this rank's one slot against one other rank's slot at a time, the same arithmetic, the partials at
+// the gather launches' places and the dZ slab accumulated block after block (launch_xview_*_block_*).
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
 #include "host_common.h"
@@ -89,6 +92,10 @@ struct XvParams {
   char* gbuf;         // [planes][n_pad][ldg bytes] G in the compute dtype (16-bit: residual plane, hi plane)
   long long ldg;
   long long plane_bytes;
+  // block form (kBlock kernels): zq is this rank's own ONE slot [rows_pad][ldb], zcol a one-slot buffer
+  // of the same shape that holds rank q_lo's rows (the own block: zq itself). q_lo is the slot's
+  // identity: it drives own = (q == rank), the positive test and the output place, no buffer index.
+  const char* zcol;
 };
 // 16-bit plans: the residual plane holds (G - hi) * kXvLoScale, clear of fp16's subnormals; the dZ
 // runs it first and scales its accumulators back (a power of two: exact) before the hi plane.
@@ -96,12 +103,14 @@ constexpr float kXvLoScale = 2048.f;
 
 // acc = tile (I, Jl of slot q) of side `side`: rows side * n + I * 128 .. of the own slot against
 // rows (1 - side) * n + Jl * 128 .. of slot q. Ends with a block barrier: the caller's epilogue may
-// reuse the staging images.
-template <typename T>
+// reuse the staging images. kBlock: the rows from the one-slot p.zq, the columns from the one-slot
+// p.zcol (rank q's rows); q does not index a buffer.
+template <typename T, bool kBlock = false>
 __device__ __forceinline__ void xv_tile_gemm(const XvParams& p, int side, int I, int q, int Jl, lds_char* lds,
                                              f32x4 (&acc)[4][4]) {
-  const char* arow = p.zq + ((long long)p.rank * p.rows_pad + (long long)side * p.n + (long long)I * kXvTile) * p.ldb;
-  const char* brow = p.zq + ((long long)q * p.rows_pad + (long long)(1 - side) * p.n + (long long)Jl * kXvTile) * p.ldb;
+  const long long aslot = kBlock ? 0 : (long long)p.rank * p.rows_pad, bslot = kBlock ? 0 : (long long)q * p.rows_pad;
+  const char* arow = p.zq + (aslot + (long long)side * p.n + (long long)I * kXvTile) * p.ldb;
+  const char* brow = (kBlock ? p.zcol : p.zq) + (bslot + (long long)(1 - side) * p.n + (long long)Jl * kXvTile) * p.ldb;
   tile128_gemm<T>(
       lds, p.nk, [&](int k) { return Tile128Src{arow + (long long)k * kKStepBytes, p.ldb}; },
       [&](int k) { return Tile128Src{brow + (long long)k * kKStepBytes, p.ldb}; }, false, Tile128Plain{}, acc);
@@ -434,7 +443,9 @@ struct XvDzParams {
   long long ldo;
 };
 
-template <typename T>
+// kAccum (the ring's later blocks): out[m][e] = out[m][e] + acc with plain loads and stores. One
+// workgroup owns each element per launch and the launches are stream-ordered: a fixed order, no atomics.
+template <typename T, bool kAccum = false>
 __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
@@ -477,7 +488,10 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
       if (m < p.n_half) {
         float* orow = out + ((long long)side * p.n_half + m) * p.ldo + (long long)Ei * kXvTile + 64 * wc + r16;
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) orow[16 * ni] = acc[mi][ni][r];
+        for (int ni = 0; ni < 4; ++ni) {
+          if constexpr (kAccum) orow[16 * ni] = orow[16 * ni] + acc[mi][ni][r];
+          else orow[16 * ni] = acc[mi][ni][r];
+        }
       }
     }
 }
@@ -550,7 +564,9 @@ __device__ __forceinline__ void xv_sig_load_pos(const XvSigParams& ps, bool diag
 // index (a pad column has cos = 0 and would add softplus(bias)). Fixed order: a lane's 64 terms, the
 // wave's 64 lanes, the four waves; fp64 from the lane on, so the loss is rounded to fp32 once, at
 // its end. One partial per tile, no atomics.
-template <typename T>
+// kBlock: the nT x nT tiles of a_r (p.zq, one slot) against b_q (p.zcol, one slot), the launch's one
+// slot q = q_lo (nq = 1, no q_skip); the tile's partial goes to the same place of lpart as below.
+template <typename T, bool kBlock = false>
 __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvSigParams ps) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
@@ -568,7 +584,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
   const bool own = q == p.rank;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, 0, I, q, Jl, lds, acc);
+  xv_tile_gemm<T, kBlock>(p, 0, I, q, Jl, lds, acc);
 
   int cl[4];
 #pragma unroll
@@ -611,7 +627,10 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
 // gradient's partials are taken from the fp32 values before they are rounded to the planes: the plane
 // image fills the whole __shared__ object, so every wave reduces in its registers and stores one
 // fp32 partial to bias_part[tile][wave].
-template <typename T>
+// kBlock: one side of the ONE block of slot q = q_lo, nT x nT tiles of the one-slot operands, stored as
+// planes [n_pad][n_pad] (J = Jl); the bias partials go to the tile's place in the n_pad x W n_pad
+// block, ((I W + q) nT + Jl) * 4 + wave, which is what b * 4 + w is below.
+template <typename T, bool kBlock = false>
 __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const XvSigParams ps) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
@@ -620,14 +639,15 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
   const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
   // tile (I, J) of one side's n_pad x W n_pad block, as xview_side_coef_kernel
-  const int ncol = p.world * p.nT;
+  const int ncol = kBlock ? p.nT : p.world * p.nT;
   const int I = b / ncol, J = b - I * ncol;
-  const int q = J / p.nT, Jl = J - q * p.nT;
+  const int q = kBlock ? p.q_lo : J / p.nT, Jl = kBlock ? J : J - q * p.nT;
   const int n = p.n;
   const bool own = q == p.rank;
+  const int bplace = kBlock ? (I * p.world + q) * p.nT + Jl : b;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, p.side, I, q, Jl, lds, acc);
+  xv_tile_gemm<T, kBlock>(p, p.side, I, q, Jl, lds, acc);
 
   constexpr bool kSplit = sizeof(T) == 2;
   constexpr int kPlaneElems = kXvTile * kXvTile;
@@ -665,7 +685,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const Xv
       }
     }
   bsum = wave_sum(bsum);
-  if (ps.bias_part && lane == 0) ps.bias_part[b * 4 + w] = bsum;  // side 0 only: each pair counts once
+  if (ps.bias_part && lane == 0) ps.bias_part[bplace * 4 + w] = bsum;  // side 0 only: each pair counts once
   __syncthreads();
   // 16-byte chunks, rows contiguous, as xview_side_coef_kernel
   constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
@@ -786,14 +806,15 @@ void xv_launch_coef(DType comp, dev::XvParams p, const Geometry& g, int side, co
 // xview_dz_kernel's arguments with K = world * n_pad per plane: the planes' rows and Zt's rows both
 // hold the rank slots side by side, so a plane's K-steps run through the slots in ascending order.
 // The dZ tiles write columns [0, En) of rows [side * n, side * n + n) of the [rows_pad][dim_n] slab.
+// kslots: the rank slots side by side in a row, g.world, or 1 for the block form (K = n_pad per plane).
 dev::XvDzParams xv_dz_params(DType comp, const void* coef, const void* zt, const Geometry& g, float* dz,
-                             const std::string& who) {
+                             const std::string& who, int kslots) {
   const size_t es = dtype_size(comp);
   const int np = xv_npad(g), en = xv_en(g);
   NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, who + ": dim_n < roundup(dim_k, 128)");
   dev::XvDzParams q{};
   q.gbuf = static_cast<const char*>(coef);
-  q.ldg = (long long)g.world * np * (long long)es;
+  q.ldg = (long long)kslots * np * (long long)es;
   q.plane_bytes = (long long)np * q.ldg;
   q.planes = xv_planes(comp);
   q.zt = static_cast<const char*>(zt);
@@ -853,7 +874,7 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream) {
   xv_params_one(comp, nullptr, g, "xview_dz");
   NTXENT_CHECK(coef && zt && dz, "xview_dz: null buffer");
-  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dz");
+  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dz", g.world);
   const int np = xv_npad(g);
   const dim3 grid(q.En / dev::kXvTile, np / dev::kXvTile);
   dispatch_comp(comp, [&](auto tc) {
@@ -1036,11 +1057,101 @@ void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Ge
                           hipStream_t stream) {
   NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1), "xview_dist_dz: bad argument");
   xv_params(comp, nullptr, g, "xview_dist_dz");
-  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dist_dz");
+  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dist_dz", g.world);
   q.side = side;
   const dim3 grid(q.En / dev::kXvTile, xv_npad(g) / dev::kXvTile);
   dispatch_comp(comp, [&](auto tc) {
     hipLaunchKernelGGL((dev::xview_dz_kernel<decltype(tc)>), grid, dim3(dev::kXvThreads), 0, stream, q);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+// ---- block form: rank g.rank against ONE rank slot at a time (the ring exchange) -----------------------
+// zq: this rank's own slot [rows_pad][ld_k]; rows_q: a buffer of the same shape that holds rank q's rows
+// (q == g.rank: zq itself). Every row a stage can read, up to local row n + n_pad <= rows_pad, lies in
+// the one slot: the buffers must be whole slots (received whole, or zero beyond what was received).
+// Nothing here has a size that depends on g.world except lpart / bias_part, which keep the gather
+// launches' layout so that the same two sums finish the loss and dL/dbias.
+namespace {
+dev::XvSigParams xv_sig_block_params(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
+                                     int q, const std::string& who) {
+  NTXENT_CHECK(0 <= q && q < g.world, who + ": slot q outside the world");
+  dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, who, false);
+  ps.x.zcol = static_cast<const char*>(rows_q);
+  ps.x.q_lo = q;
+  ps.x.nq = 1;
+  ps.x.q_skip = -1;
+  return ps;
+}
+}  // namespace
+
+size_t xview_block_coef_bytes(DType comp, const Geometry& g) {
+  return (size_t)xv_planes(comp) * xv_npad(g) * xv_npad(g) * dtype_size(comp);
+}
+size_t xview_block_zt_bytes(DType comp, const Geometry& g) {
+  return (size_t)2 * xv_en(g) * xv_npad(g) * dtype_size(comp);
+}
+
+void launch_xview_sigmoid_block_fwd(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias, int q,
+                                    double* lpart, hipStream_t stream, const float* pos_cos) {
+  NTXENT_CHECK(zq && rows_q && lpart, "xview_sigmoid_block_fwd: null buffer");
+  dev::XvSigParams ps = xv_sig_block_params(comp, zq, rows_q, g, bias, q, "xview_sigmoid_block_fwd");
+  ps.pos_cos = q == g.rank ? pos_cos : nullptr;  // the own block alone holds positives
+  ps.lpart = lpart;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc), true>), dim3(ps.x.nT * ps.x.nT), dim3(dev::kXvThreads),
+                       0, stream, ps);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_sigmoid_block_coef(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
+                                     int q, int side, void* coef, float* bias_part, hipStream_t stream,
+                                     const float* pos_cos) {
+  NTXENT_CHECK(zq && rows_q && coef && (side == 0 || side == 1), "xview_sigmoid_block_coef: bad argument");
+  NTXENT_CHECK((side == 0) == (bias_part != nullptr), "xview_sigmoid_block_coef: bias_part with side 0 and only there");
+  dev::XvSigParams ps = xv_sig_block_params(comp, zq, rows_q, g, bias, q, "xview_sigmoid_block_coef");
+  ps.pos_cos = q == g.rank ? pos_cos : nullptr;
+  ps.x.side = side;
+  ps.x.gbuf = static_cast<char*>(coef);
+  ps.x.ldg = (long long)xv_npad(g) * (long long)dtype_size(comp);
+  ps.x.plane_bytes = (long long)xv_npad(g) * ps.x.ldg;
+  ps.bias_part = bias_part;
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<decltype(tc), true>), dim3(ps.x.nT * ps.x.nT), dim3(dev::kXvThreads),
+                       0, stream, ps);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_block_zt(DType comp, const void* rows_q, const Geometry& g, void* zt, hipStream_t stream) {
+  NTXENT_CHECK(rows_q && zt, "xview_block_zt: null buffer");
+  xv_params(comp, rows_q, g, "xview_block_zt");
+  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
+  // one slot: blockIdx.z = v, so the slot strides are never applied
+  dispatch_comp(comp, [&](auto tc) {
+    using Tc = decltype(tc);
+    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2), dim3(256), 0, stream,
+                       static_cast<const Tc*>(rows_q), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
+                       (long long)np, (long long)g.rows_pad, (long long)np);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+void launch_xview_block_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
+                           bool accumulate, hipStream_t stream) {
+  NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1), "xview_block_dz: bad argument");
+  xv_params(comp, nullptr, g, "xview_block_dz");
+  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_block_dz", 1);
+  q.side = side;
+  const dim3 grid(q.En / dev::kXvTile, xv_npad(g) / dev::kXvTile);
+  dispatch_comp(comp, [&](auto tc) {
+    using Tc = decltype(tc);
+    if (accumulate) {
+      hipLaunchKernelGGL((dev::xview_dz_kernel<Tc, true>), grid, dim3(dev::kXvThreads), 0, stream, q);
+    } else {
+      hipLaunchKernelGGL((dev::xview_dz_kernel<Tc, false>), grid, dim3(dev::kXvThreads), 0, stream, q);
+    }
   });
   NTXENT_HIP_CHECK(hipGetLastError());
 }

@@ -628,6 +628,124 @@ std::tuple<at::Tensor, at::Tensor> xview_sigmoid_dist_backward(const at::Tensor&
   return {dh, shares};
 }
 
+// ---- the same loss, one rank slot at a time (exchange="ring"): stage ops shared by
+// parallel/sigmoid.py's RingSigmoidFunction and parallel/emulate.py -----------------------------------
+// zq [rows_pad, ld_k]: this rank's own prep rows; rows_q: the same shape, rank q's rows (q == rank: zq).
+static void check_xview_block(const at::Tensor& zq, const at::Tensor& rows_q, int q, const Plan& P) {
+  check_input(zq, "zq");
+  check_input(rows_q, "rows_q");
+  NTXENT_CHECK(P.comp != DType::FP8, "xview_block: fp32 | fp16 | bf16 plans (these kernels have no fp8 operands)");
+  const long want = (long)P.g.rows_pad * P.g.ld_k;
+  NTXENT_CHECK(zq.numel() == want && zq.scalar_type() == to_scalar(P.comp) && rows_q.numel() == want &&
+                   rows_q.scalar_type() == to_scalar(P.comp),
+               "zq and rows_q must be [rows_pad, ld_k] in the plan's compute dtype (whole rank slots)");
+  NTXENT_CHECK(0 <= q && q < P.g.world, "slot q outside the world");
+}
+
+// 16-bit plans: the pairs' cosines of this rank's rows (sigmoid_pos_cos), the own block's diagonal in
+// the block backward; undefined (None) for fp32 plans.
+c10::optional<at::Tensor> xview_sigmoid_pos_cos(const at::Tensor& h, const at::Tensor& inv, const Plan& P) {
+  check_input(h, "h");
+  const Geometry& g = P.g;
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows]");
+  const at::DeviceGuard guard(h.device());
+  const at::Tensor pos = sigmoid_pos_cos(h, inv, P.comp, g);
+  if (!pos.defined()) return c10::nullopt;
+  return pos;
+}
+
+// Side 0's nT x nT tiles of a_r against b_q into the caller's lpart (float64 [xview_sigmoid_dist_tiles]),
+// each at the place the gather launch gives it: after all W blocks xview_sigmoid_dist_loss serves as
+// it is. h, inv: a 16-bit plan's own block (q == rank) takes the positives' cosines from them.
+void xview_sigmoid_block_fwd(const at::Tensor& zq, const at::Tensor& rows_q, int q, const Plan& P, at::Tensor& lpart,
+                             const at::Tensor& h, const at::Tensor& inv, double bias) {
+  check_xview_block(zq, rows_q, q, P);
+  check_input(lpart, "lpart");
+  check_input(h, "h");
+  const Geometry& g = P.g;
+  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(g) && lpart.scalar_type() == at::kDouble,
+               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows]");
+  const at::DeviceGuard guard(zq.device());
+  const at::Tensor pos = q == g.rank ? sigmoid_pos_cos(h, inv, P.comp, g) : at::Tensor();
+  launch_xview_sigmoid_block_fwd(P.comp, zq.data_ptr(), rows_q.data_ptr(), g, (float)bias, q, lpart.data_ptr<double>(),
+                                 cur_stream(zq), pos.defined() ? pos.data_ptr<float>() : nullptr);
+}
+
+// One block of the backward: rows_q transposed into zt, then for side 0 and side 1 the coefficient
+// block into coef and its product added to (first: stored in) the fp32 slab dz. coef
+// (xview_block_coef_bytes), zt (xview_block_zt_bytes), bias_part (xview_sigmoid_bias_part_bytes / 4
+// floats) and dz (xview_dz_bytes / 4 floats) are the caller's and are reused across blocks; none
+// needs initialisation. pos_cos: xview_sigmoid_pos_cos's (None for fp32 plans).
+void xview_sigmoid_block_backward(const at::Tensor& zq, const at::Tensor& rows_q, int q, const Plan& P, double bias,
+                                  at::Tensor& coef, at::Tensor& zt, at::Tensor& bias_part, at::Tensor& dz,
+                                  const c10::optional<at::Tensor>& pos_cos, bool first) {
+  check_xview_block(zq, rows_q, q, P);
+  check_input(coef, "coef");
+  check_input(zt, "zt");
+  check_input(bias_part, "bias_part");
+  check_input(dz, "dz");
+  const Geometry& g = P.g;
+  NTXENT_CHECK(coef.numel() * coef.element_size() == (long)xview_block_coef_bytes(P.comp, g),
+               "coef must hold xview_block_coef_bytes");
+  NTXENT_CHECK(zt.numel() * zt.element_size() == (long)xview_block_zt_bytes(P.comp, g),
+               "zt must hold xview_block_zt_bytes");
+  NTXENT_CHECK(bias_part.numel() * 4 == (long)xview_sigmoid_bias_part_bytes(g) && bias_part.scalar_type() == at::kFloat,
+               "bias_part must be float32 [n_pad / 128 * world * n_pad / 128 * 4]");
+  NTXENT_CHECK(dz.numel() * 4 == (long)xview_dz_bytes(g) && dz.scalar_type() == at::kFloat,
+               "dz must be float32 [rows_pad * dim_n]");
+  const float* pos = nullptr;
+  if (pos_cos.has_value() && pos_cos->defined()) {
+    check_input(*pos_cos, "pos_cos");
+    NTXENT_CHECK(pos_cos->numel() == g.rows / 2 && pos_cos->scalar_type() == at::kFloat, "pos_cos must be float32 [rows / 2]");
+    pos = pos_cos->data_ptr<float>();
+  }
+  NTXENT_CHECK((pos != nullptr) == (P.comp != DType::F32), "pos_cos with 16-bit plans and only there");
+  const at::DeviceGuard guard(zq.device());
+  const hipStream_t stream = cur_stream(zq);
+  launch_xview_block_zt(P.comp, rows_q.data_ptr(), g, zt.data_ptr(), stream);
+  for (int side = 0; side < 2; ++side) {
+    launch_xview_sigmoid_block_coef(P.comp, zq.data_ptr(), rows_q.data_ptr(), g, (float)bias, q, side, coef.data_ptr(),
+                                    side == 0 ? bias_part.data_ptr<float>() : nullptr, stream, pos);
+    launch_xview_block_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), !first, stream);
+  }
+}
+
+// After all W blocks: the normalisation backward of the slab with the global scale, and the fp64 shares
+// as xview_sigmoid_dist_backward forms them. Returns (dh, shares); shares undefined if neither is wanted.
+std::tuple<at::Tensor, at::Tensor> xview_sigmoid_ring_finish(const at::Tensor& h, const at::Tensor& inv,
+                                                             const at::Tensor& grad_out, const at::Tensor& dz,
+                                                             const at::Tensor& bias_part, const Plan& P, bool want_tau,
+                                                             bool want_bias) {
+  check_input(h, "h");
+  check_input(dz, "dz");
+  check_input(bias_part, "bias_part");
+  const Geometry& g = P.g;
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat,
+               "xview_sigmoid_ring_finish: inv must be float32 [rows]");
+  NTXENT_CHECK(dz.numel() * 4 == (long)xview_dz_bytes(g) && dz.scalar_type() == at::kFloat,
+               "dz must be float32 [rows_pad * dim_n]");
+  NTXENT_CHECK(bias_part.numel() * 4 == (long)xview_sigmoid_bias_part_bytes(g) && bias_part.scalar_type() == at::kFloat,
+               "bias_part must be float32 [n_pad / 128 * world * n_pad / 128 * 4]");
+  const at::DeviceGuard guard(h.device());
+  const hipStream_t stream = cur_stream(h);
+  auto go = grad_scalar(grad_out);
+  at::Tensor none_a, none_b, dot, shares;  // the caller owns coef and zt
+  auto dh = xview_backward_tail(h, inv, go, dz, none_a, none_b, g, stream, &dot);
+  if (want_tau || want_bias) {
+    shares = at::zeros({2}, opts(h, at::kDouble));
+    if (want_tau)
+      launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream, shares.data_ptr<double>());
+    if (want_bias)
+      launch_xview_sigmoid_bias_grad(bias_part.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream,
+                                     shares.data_ptr<double>() + 1);
+  }
+  return {dh, shares};
+}
+
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {
   check_input(zq, "zq");
   const at::DeviceGuard guard(zq.device());
@@ -1660,6 +1778,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xview_sigmoid_dist_loss", &xview_sigmoid_dist_loss, py::arg("lpart"), py::arg("plan"));
   m.def("xview_sigmoid_dist_backward", &xview_sigmoid_dist_backward, py::arg("h"), py::arg("zq_all"), py::arg("inv"),
         py::arg("grad_out"), py::arg("plan"), py::arg("bias"), py::arg("want_tau"), py::arg("want_bias"));
+  // block form (exchange="ring"): the caller's buffers, in bytes / elements
+  m.def("xview_sigmoid_block_sizes", [](const Plan& P) {
+    py::dict d;
+    d["coef_bytes"] = (long)xview_block_coef_bytes(P.comp, P.g);
+    d["zt_bytes"] = (long)xview_block_zt_bytes(P.comp, P.g);
+    d["bias_part"] = (long)(xview_sigmoid_bias_part_bytes(P.g) / 4);
+    d["dz"] = (long)(xview_dz_bytes(P.g) / 4);
+    d["gather_coef_bytes"] = (long)xview_coef_bytes(P.comp, P.g);
+    d["gather_zt_bytes"] = (long)xview_zt_bytes(P.comp, P.g);
+    return d;
+  });
+  m.def("xview_sigmoid_pos_cos", &xview_sigmoid_pos_cos, py::arg("h"), py::arg("inv"), py::arg("plan"));
+  m.def("xview_sigmoid_block_fwd", &xview_sigmoid_block_fwd, py::arg("zq"), py::arg("rows_q"), py::arg("q"),
+        py::arg("plan"), py::arg("lpart"), py::arg("h"), py::arg("inv"), py::arg("bias"));
+  m.def("xview_sigmoid_block_backward", &xview_sigmoid_block_backward, py::arg("zq"), py::arg("rows_q"), py::arg("q"),
+        py::arg("plan"), py::arg("bias"), py::arg("coef"), py::arg("zt"), py::arg("bias_part"), py::arg("dz"),
+        py::arg("pos_cos"), py::arg("first"));
+  m.def("xview_sigmoid_ring_finish", &xview_sigmoid_ring_finish, py::arg("h"), py::arg("inv"), py::arg("grad_out"),
+        py::arg("dz"), py::arg("bias_part"), py::arg("plan"), py::arg("want_tau"), py::arg("want_bias"));
   m.def("tile_list_uploads", []() { return g_tile_uploads.load(); });
   m.def("set_small_path", &ntxent::set_small_path, py::arg("on"));
   m.def("small_path_enabled", &ntxent::small_path_enabled);

@@ -98,17 +98,22 @@ def emulated_xview_forward_backward(shards: Sequence[torch.Tensor], temperature:
 
 def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperature: float, bias: float, *,
                                       compute: str = "auto", grad_out: float = 1.0, want_tau: bool = True,
-                                      want_bias: bool = True):
+                                      want_bias: bool = True, exchange: str = "gather"):
     """Distributed pairwise sigmoid loss (:mod:`parallel.sigmoid`) for W virtual ranks on one device:
     ``(loss, grads, dtau, dbias)`` for shards h_r = [a_r; b_r]: the loss of the global batch in pair
     order, per-rank dL/dh_r, and the two scalar gradients (0-d fp32), all times ``grad_out``. Every
     rank's prep writes its slot of the shared ``zq_all``; the fp64 shares of the loss and of the
     scalar gradients are summed as the all-reduces would and rounded to fp32 once. A scalar gradient
     that is not wanted is None (with neither the backward stage returns no shares, as a backward
-    that does not communicate)."""
+    that does not communicate). ``exchange="ring"`` drives the ring stage ops instead: every rank's
+    prep writes a buffer of its own, and a rank's ``visit`` hands it the other virtual ranks' ``zq`` in
+    ring order, q = r, r-1, ..., r-W+1, without copying."""
     from .infonce import _CDT, xview_compute
-    from .sigmoid import sigmoid_stage_forward
+    from .sigmoid import (EXCHANGES, sigmoid_ring_stage_backward, sigmoid_ring_stage_forward,
+                          sigmoid_stage_forward)
 
+    if exchange not in EXCHANGES:
+        raise ValueError(f"emulated_sigmoid_forward_backward: exchange must be one of {EXCHANGES}, got {exchange!r}")
     C = _ext.load()
     W = len(shards)
     R, d = shards[0].shape
@@ -117,6 +122,29 @@ def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperatur
     plans = [C.get_plan(R, d, W, r, float(temperature), comp, dev.index) for r in range(W)]
     Rpad = plans[0].rows_pad
     hs = [x.contiguous() for x in shards]
+    if exchange == "ring":
+        preps = [C.prep(hs[r], plans[r]) for r in range(W)]
+        zqs = [p[0] for p in preps]
+
+        def visit_of(r):
+            def visit(fn):
+                for s in range(W):
+                    fn((r - s) % W, zqs[(r - s) % W], 0)
+            return visit
+
+        loss = torch.zeros((), dtype=torch.float64, device=dev)
+        for r in range(W):
+            loss = loss + sigmoid_ring_stage_forward(C, plans[r], zqs[r], hs[r], preps[r][1], float(bias), visit_of(r))
+        go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
+        grads, scalars = [], torch.zeros((2,), dtype=torch.float64, device=dev)
+        for r in range(W):
+            dh, shares = sigmoid_ring_stage_backward(C, plans[r], zqs[r], hs[r], preps[r][1], float(bias), go,
+                                                     bool(want_tau), bool(want_bias), visit_of(r))
+            grads.append(dh)
+            if shares is not None:
+                scalars = scalars + shares  # "all-reduce" (fp64 shares)
+        scalars = scalars.float()
+        return loss.float(), grads, scalars[0] if want_tau else None, scalars[1] if want_bias else None
     zq_all = torch.empty((W * Rpad, plans[0].ld_k), dtype=_CDT[comp], device=dev)
     preps = [C.prep(hs[r], plans[r], zq_all[r * Rpad:(r + 1) * Rpad], None) for r in range(W)]  # "all-gather"
     loss = torch.zeros((), dtype=torch.float64, device=dev)

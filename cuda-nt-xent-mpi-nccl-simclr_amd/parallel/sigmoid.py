@@ -25,6 +25,17 @@ every rank (not checked).
 Bytes across ranks per step and rank: the gather of ``(W - 1) Rpad ld_k`` elements of the compute
 dtype, 8 B for the loss, 16 B for the scalar gradients.
 
+``exchange="ring"`` (``RingSigmoidFunction``) holds no buffer of W slots. Every pair is a binary term of
+its own, so nothing has to be agreed between ranks and a rank never needs more than one other rank's
+rows at a time: rank r works on the slots q = r, r-1, ..., r-W+1 while the next one travels
+(``ring._ring``), in the forward and again in the backward. Per rank: the own ``zq [Rpad][ld_k]`` (the
+only unit rows saved), two ring buffers of that size, one coefficient block ``[planes][n_pad][n_pad]``,
+one ``zt [2][En][n_pad]``, the fp32 dZ slab (stored by the first block, added to by the later ones) and
+the tiles' partials ``lpart`` / ``bias_part`` (``nT W nT`` entries, at the gather launches' places:
+the loss share and the dL/dbias share are bitwise the gather path's). Both sides are still computed
+locally and no gradient crosses ranks. Bytes across ranks per step and rank: ``2 (W - 1) Rpad ld_k``
+elements, twice the gather's, and the same 8 B and 16 B.
+
 ``csrc/kernels/xview_kernels.hip`` (the ``xview_sigmoid_*`` kernels); the stage ops are shared with
 ``parallel/emulate.emulated_sigmoid_forward_backward``.
 """
@@ -41,6 +52,7 @@ from ..ops.sigmoid import _host_values, sigmoid_loss
 from .commstats import span
 from .distributed import _all_gather_into, _world
 from .infonce import _CDT, _gather, xview_compute
+from .ring import _ring
 
 
 def sigmoid_stage_forward(C, plan, zq_all: torch.Tensor, h: torch.Tensor, inv: torch.Tensor, bias: float, wait=None):
@@ -111,9 +123,95 @@ class DistSigmoidFunction(torch.autograd.Function):
         return dh, None, None, None, None, None, dtau, dbias
 
 
+# ---------------------------------------------------------------------------------------
+# exchange="ring": one rank slot at a time, O(local) memory
+# ---------------------------------------------------------------------------------------
+def sigmoid_ring_stage_forward(C, plan, zq: torch.Tensor, h: torch.Tensor, inv: torch.Tensor, bias: float, visit):
+    """One rank's forward over the blocks ``visit`` hands it. ``visit(fn)`` is the transport: it calls
+    ``fn(q, rows_q, ...)`` once per rank slot q in ring order (q = r, r-1, ..., r-W+1), ``rows_q
+    [Rpad][ld_k]`` holding rank q's unit rows (the own block: ``zq`` itself). Every tile writes the
+    place of ``lpart`` the gather launches give it, so the share is bitwise ``sigmoid_stage_forward``'s.
+    Returns the rank's share of the loss, a 0-d float64 tensor."""
+    lpart = torch.empty((C.xview_sigmoid_dist_tiles(plan),), dtype=torch.float64, device=zq.device)
+    visit(lambda q, rows_q, *_: C.xview_sigmoid_block_fwd(zq, rows_q, q, plan, lpart, h, inv, bias))
+    return C.xview_sigmoid_dist_loss(lpart, plan)
+
+
+def sigmoid_ring_stage_backward(C, plan, zq: torch.Tensor, h: torch.Tensor, inv: torch.Tensor, bias: float,
+                                grad_out: torch.Tensor, want_tau: bool, want_bias: bool, visit):
+    """One rank's backward over the same blocks: per block the transpose, and per side the coefficient
+    block ``[planes][n_pad][n_pad]`` and its dZ rows, stored by the first block and added by the later
+    ones (stream-ordered, no atomics). One ``coef``, one ``zt`` and the fp32 slab serve every block; only
+    ``bias_part`` (``nT * W * nT * 4`` floats) grows with W. Returns ``(dh, shares)`` as
+    ``xview_sigmoid_dist_backward`` does; the dL/dbias share is bitwise its own, ``dh`` and the dL/dtau
+    share are sums in block order, not slot order."""
+    size = C.xview_sigmoid_block_sizes(plan)
+    dev = zq.device
+    coef = torch.empty((size["coef_bytes"],), dtype=torch.uint8, device=dev)
+    zt = torch.empty((size["zt_bytes"],), dtype=torch.uint8, device=dev)
+    bias_part = torch.empty((size["bias_part"],), dtype=torch.float32, device=dev)
+    dz = torch.empty((size["dz"],), dtype=torch.float32, device=dev)
+    pos = C.xview_sigmoid_pos_cos(h, inv, plan)
+    first = [True]
+
+    def block(q, rows_q, *_):
+        C.xview_sigmoid_block_backward(zq, rows_q, q, plan, bias, coef, zt, bias_part, dz, pos, first[0])
+        first[0] = False
+
+    visit(block)
+    del coef, zt
+    return C.xview_sigmoid_ring_finish(h, inv, grad_out, dz, bias_part, plan, want_tau, want_bias)
+
+
+class RingSigmoidFunction(torch.autograd.Function):
+    """``DistSigmoidFunction`` with the rows passed around the ring (``ring._ring``) in both directions
+    of the step: only ``h``, the own ``zq`` and ``inv`` are saved."""
+
+    @staticmethod
+    def forward(ctx, h: torch.Tensor, temperature: float, bias: float, compute: str, group,
+                tau: Optional[torch.Tensor] = None, bias_t: Optional[torch.Tensor] = None):
+        C = _ext.load()
+        W, r = _world(group)
+        h = h.contiguous()
+        R, d = h.shape
+        plan = C.get_plan(R, d, W, r, float(temperature), compute, h.device.index)
+        # whole slots travel: prep zero-fills the K padding and the pad rows, so every row a tile stage
+        # can read from a ring buffer has been received
+        zq, inv, _, _ = C.prep(h, plan)
+        share = sigmoid_ring_stage_forward(C, plan, zq, h, inv, float(bias), lambda fn: _ring(zq, group, fn))
+        if W > 1:
+            with span("sigmoid_loss"):
+                dist.all_reduce(share, op=dist.ReduceOp.SUM, group=group)  # fp64 shares (8 B)
+        ctx.plan, ctx.bias, ctx.group = plan, float(bias), group
+        ctx.tau = _tau_like(tau)
+        ctx.bias_like = _tau_like(bias_t)
+        ctx.save_for_backward(h, zq, inv)
+        return share.float()
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        h, zq, inv = ctx.saved_tensors
+        want_tau = ctx.tau is not None and ctx.needs_input_grad[5]
+        want_bias = ctx.bias_like is not None and ctx.needs_input_grad[6]
+        dh, shares = sigmoid_ring_stage_backward(_ext.load(), ctx.plan, zq, h, inv, ctx.bias, grad_out.reshape(1),
+                                                 want_tau, want_bias, lambda fn: _ring(zq, ctx.group, fn))
+        dtau = dbias = None
+        if want_tau or want_bias:
+            if ctx.plan.world > 1:
+                with span("sigmoid_scalars"):
+                    dist.all_reduce(shares, op=dist.ReduceOp.SUM, group=ctx.group)  # fp64 shares (16 B)
+            both = shares.float()
+            dtau = _tau_grad(both[0], ctx.tau) if want_tau else None
+            dbias = _tau_grad(both[1], ctx.bias_like) if want_bias else None
+        return dh, None, None, None, None, dtau, dbias
+
+
+EXCHANGES = ("gather", "ring")
+
+
 def dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, *, z2: Optional[torch.Tensor] = None,
                       group=None, compute: str = "auto", use_mixed_precision: bool = False,
-                      overlap: bool = True) -> torch.Tensor:
+                      overlap: bool = True, exchange: str = "gather") -> torch.Tensor:
     """Global pairwise sigmoid loss over the data-parallel group; ``h_local = [a_r; b_r]`` on each
     rank (or ``h_local = a_r, z2 = b_r``), the same n and d on every rank.
 
@@ -123,20 +221,30 @@ def dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, *, z2:
       and dh are bitwise those of the same floats.
     compute: ``auto|fp32|fp16|bf16|fp8`` as for ``sigmoid_loss`` (``fp8`` computes in fp16).
     overlap: launch the tiles of the own column block before the row gather is waited for (the same
-      bits either way).
+      bits either way). Ignored by ``exchange="ring"``, whose every block but the last runs while the
+      next one travels.
+    exchange: ``"gather"`` (the default) all-gathers the unit rows once and keeps them for the
+      backward; ``"ring"`` passes one rank's rows around the ring at a time, in the forward and again
+      in the backward, and holds nothing whose size grows with the world size but the tiles' partial
+      sums: the same loss (bitwise) and dL/dbias (bitwise before the all-reduce), ``dh`` and dL/dtau
+      summed in block order. Anything else raises ``ValueError``.
     Without a process group, or in a group of one, this is ``sigmoid_loss``. CPU tensors take
     ``cpu_dist_sigmoid_loss``.
     """
+    if exchange not in EXCHANGES:
+        raise ValueError(f"dist_sigmoid_loss: exchange must be one of {EXCHANGES}, got {exchange!r}")
     W, _ = _world(group)
     if W == 1:
         return sigmoid_loss(h_local, temperature, bias, z2=z2, compute=compute, use_mixed_precision=use_mixed_precision)
     h = _stack_views(h_local, z2)
     if not h.is_cuda:
-        return cpu_dist_sigmoid_loss(h, temperature, bias, group=group)
+        return cpu_dist_sigmoid_loss(h, temperature, bias, group=group, exchange=exchange)
     comp = xview_compute(h.dtype, use_mixed_precision, compute)
     tv, bv = _host_values(temperature, bias)
     tau = temperature if temperature_wants_grad(temperature) else None
     bias_t = bias if temperature_wants_grad(bias) else None
+    if exchange == "ring":
+        return RingSigmoidFunction.apply(h, tv, bv, comp, group, tau, bias_t)
     return DistSigmoidFunction.apply(h, tv, bv, comp, group, bool(overlap), tau, bias_t)
 
 
@@ -146,12 +254,16 @@ class DistSigmoidLoss(_TemperatureModule):
     ``learnable_temperature`` / ``temperature_bounds`` / ``learnable_bias`` as ``SigmoidLoss``. The
     parameters' gradients are those of the global loss, the same on every rank: they need no further
     reduction (and, under a trainer that scales the loss by the world size for DDP's mean, are
-    scaled with it)."""
+    scaled with it). ``exchange``: ``"gather"`` or ``"ring"``, as ``dist_sigmoid_loss``'s (``overlap`` is
+    ignored by the ring)."""
 
     def __init__(self, temperature: float = 0.1, bias: float = -10.0, compute: str = "auto", group=None,
                  use_mixed_precision: bool = False, overlap: bool = True, learnable_temperature: bool = False,
-                 temperature_bounds=(0.01, 1.0), learnable_bias: bool = False):
+                 temperature_bounds=(0.01, 1.0), learnable_bias: bool = False, exchange: str = "gather"):
         super().__init__()
+        if exchange not in EXCHANGES:
+            raise ValueError(f"DistSigmoidLoss: exchange must be one of {EXCHANGES}, got {exchange!r}")
+        self.exchange = exchange
         self.compute = compute
         self.group = group
         self.use_mixed_precision = use_mixed_precision
@@ -167,11 +279,12 @@ class DistSigmoidLoss(_TemperatureModule):
     def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
         return dist_sigmoid_loss(z1, self.current_temperature(), self.bias, z2=z2, group=self.group,
                                  compute=self.compute, use_mixed_precision=self.use_mixed_precision,
-                                 overlap=self.overlap)
+                                 overlap=self.overlap, exchange=self.exchange)
 
     def extra_repr(self) -> str:
         return (f"temperature={self.temperature}, bias={self.initial_bias}, compute={self.compute}"
-                + self._temperature_repr() + (", learnable_bias=True" if self.learnable_bias else ""))
+                + self._temperature_repr() + (", learnable_bias=True" if self.learnable_bias else "")
+                + (f", exchange={self.exchange}" if self.exchange != "gather" else ""))
 
 
 # ---------------------------------------------------------------------------------------
@@ -229,10 +342,82 @@ class _CpuDistSigmoidFn(torch.autograd.Function):
         return dh, None, None, None, dtau, dbias
 
 
-def cpu_dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, group=None) -> torch.Tensor:
-    """The distributed algorithm in torch ops over gloo, for CPU tensors (any float dtype)."""
+class _CpuRingSigmoidFn(torch.autograd.Function):
+    """The ring variant: the unit rows of one rank at a time over gloo send / recv (``ring._ring``), in the
+    block order q = r, r-1, ..., r-W+1 of the GPU path, forward and backward; the towers are never
+    concatenated, and only ``z`` and ``inv`` are saved."""
+
+    @staticmethod
+    def forward(ctx, h, temperature, bias, group, tau, bias_t):
+        W, r = _world(group)
+        n = h.shape[0] // 2
+        z, inv = reference.normalize(h)
+        ar = torch.arange(n)
+        total = [torch.zeros((), dtype=z.dtype)]
+
+        def block(q, zq, *_):  # side 0 only: every global pair once
+            x = z[:n] @ zq[n:].t() / temperature + bias
+            s = -torch.ones_like(x)
+            if q == r:
+                s[ar, ar] = 1.0
+            total[0] = total[0] + torch.nn.functional.softplus(-s * x).sum()
+
+        _ring(z, group, block)
+        loss = total[0] / (W * n)
+        if W > 1:
+            dist.all_reduce(loss, group=group)
+        ctx.save_for_backward(z, inv)
+        ctx.meta = (temperature, bias, W, r, group, _tau_like(tau), _tau_like(bias_t))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, inv = ctx.saved_tensors
+        temperature, bias, W, r, group, tau_like, bias_like = ctx.meta
+        n = z.shape[0] // 2
+        N = W * n
+        ar = torch.arange(n)
+        dz = torch.zeros_like(z)
+        sums = torch.zeros(2, dtype=z.dtype)  # side 0's sum of G cos and of G: each pair counts once
+
+        def block(q, zq, *_):
+            for v in (0, 1):  # side 1: the same formula with the roles swapped gives the rows of G^T
+                other = zq[(1 - v) * n:(2 - v) * n]
+                cos = z[v * n:(v + 1) * n] @ other.t()
+                x = cos / temperature + bias
+                G = torch.sigmoid(x)
+                if q == r:
+                    G[ar, ar] = -torch.sigmoid(-x[ar, ar])
+                dz[v * n:(v + 1) * n] += G @ other
+                if v == 0:
+                    sums[0] += (G * cos).sum()
+                    sums[1] += G.sum()
+
+        _ring(z, group, block)
+        dz = dz * (g / (N * temperature))
+        dot = (z * dz).sum(1, keepdim=True)
+        dh = inv.unsqueeze(1) * (dz - z * dot)
+        want_tau = tau_like is not None and ctx.needs_input_grad[4]
+        want_bias = bias_like is not None and ctx.needs_input_grad[5]
+        dtau = dbias = None
+        if want_tau or want_bias:
+            shares = torch.stack([-sums[0] / (N * temperature * temperature), sums[1] / N]).double() * g.double()
+            if W > 1:
+                dist.all_reduce(shares, group=group)
+            dtau = _tau_grad(shares[0], tau_like) if want_tau else None
+            dbias = _tau_grad(shares[1], bias_like) if want_bias else None
+        return dh, None, None, None, dtau, dbias
+
+
+def cpu_dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, group=None,
+                          exchange: str = "gather") -> torch.Tensor:
+    """The distributed algorithm in torch ops over gloo, for CPU tensors (any float dtype);
+    ``exchange`` as ``dist_sigmoid_loss``'s."""
+    if exchange not in EXCHANGES:
+        raise ValueError(f"cpu_dist_sigmoid_loss: exchange must be one of {EXCHANGES}, got {exchange!r}")
     h = _stack_views(h_local, None)
     tv, bv = _host_values(temperature, bias)
     tau = temperature if temperature_wants_grad(temperature) else None
     bias_t = bias if temperature_wants_grad(bias) else None
-    return _CpuDistSigmoidFn.apply(h, tv, bv, group, tau, bias_t)
+    fn = _CpuRingSigmoidFn if exchange == "ring" else _CpuDistSigmoidFn
+    return fn.apply(h, tv, bv, group, tau, bias_t)

@@ -29,6 +29,11 @@ same run: the op; the eager PyTorch expression of the same per-rank work in the 
 and one rank of ``dist_info_nce_loss`` on the same rows. ``--memory`` records instead the
 torch.cuda.max_memory_allocated delta of one emulated rank's step at W = 2, n = 1024, d = 512, fp16,
 for both losses.
+
+  python tools/sigmoid_cost.py --world W --exchange ring [--out profiles/sigmoid_ring/sigmoid_cost_wW.json]
+
+times one virtual rank's stage ops of ``exchange="ring"`` beside the gather ones, in one process, in
+alternating rounds, on the same device-filled rows, and records both modes' peak bytes.
 """
 from __future__ import annotations
 
@@ -188,6 +193,81 @@ def world_cost(args, dev):
     return doc
 
 
+def ring_cost(args, dev):
+    """``--world W --exchange ring``: one virtual rank's forward + backward stage ops of both exchanges in
+    one process, in alternating rounds, on the same device-filled rows (no transfer is timed: the ring's
+    blocks are the other ranks' slots, visited in ring order). Medians, and the peak bytes of one step
+    of each above the rows that are there before it (the gather's W slots, of which the ring needs its
+    own and two buffers)."""
+    from ntxent_amd.ops import _ext
+    from ntxent_amd.parallel.sigmoid import (sigmoid_ring_stage_backward, sigmoid_ring_stage_forward,
+                                             sigmoid_stage_forward)
+
+    C = _ext.load()
+    W, r = args.world, args.world // 2
+    doc = {"device": torch.cuda.get_device_name(0), "dtype": "fp16", "temperature": TAU, "bias": BIAS,
+           "iters": args.iters, "rounds": args.rounds, "world": W, "rank": r, "shapes": {}}
+    for name, batch, dim in WORLD_SHAPES:
+        plans, hs, zq_all, Rpad = _rank_setup(C, W, batch, dim, dev)
+        plan, h = plans[r], hs[r]
+        slots = [zq_all[q * Rpad:(q + 1) * Rpad] for q in range(W)]
+        go = torch.ones(1, dtype=torch.float32, device=dev)
+
+        def visit(fn):
+            for s in range(W):
+                fn((r - s) % W, slots[(r - s) % W], 0)
+
+        def gather_forward():
+            _, inv, _, _ = C.prep(h, plan, slots[r], None)
+            return inv, sigmoid_stage_forward(C, plan, zq_all, h, inv, BIAS)
+
+        def gather():
+            inv, _ = gather_forward()
+            return C.xview_sigmoid_dist_backward(h, zq_all, inv, go, plan, BIAS, True, True)
+
+        def ring_forward():
+            _, inv, _, _ = C.prep(h, plan, slots[r], None)
+            return inv, sigmoid_ring_stage_forward(C, plan, slots[r], h, inv, BIAS, visit)
+
+        def ring():
+            inv, _ = ring_forward()
+            return sigmoid_ring_stage_backward(C, plan, slots[r], h, inv, BIAS, go, True, True, visit)
+
+        arms = {"gather": gather, "ring": ring, "gather_forward": gather_forward, "ring_forward": ring_forward}
+        for fn in arms.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in arms}
+        for _ in range(args.rounds):
+            for k, fn in arms.items():
+                ms[k] += time_arm(fn, args.iters)
+        mem = {k: peak_delta(arms[k]) for k in ("gather", "ring")}
+        slot_bytes = Rpad * plan.ld_k * 2
+        rec = {k: summary(v) for k, v in ms.items()}
+        dg, dr = gather(), ring()
+        rec.update(batch=batch, dim=dim, rows=2 * batch, world=W,
+                   ring_over_gather=rec["ring"]["median_ms"] / rec["gather"]["median_ms"],
+                   ring_forward_over_gather_forward=rec["ring_forward"]["median_ms"] / rec["gather_forward"]["median_ms"],
+                   stage_peak_bytes_gather=mem["gather"], stage_peak_bytes_ring=mem["ring"], slot_bytes=slot_bytes,
+                   # with the rows each mode holds: W slots, or the own slot and two ring buffers
+                   rank_peak_bytes_gather=mem["gather"] + W * slot_bytes, rank_peak_bytes_ring=mem["ring"] + 3 * slot_bytes,
+                   bytes_across_ranks_gather=(W - 1) * slot_bytes, bytes_across_ranks_ring=2 * (W - 1) * slot_bytes,
+                   loss_share_equal=bool(torch.equal(gather_forward()[1], ring_forward()[1])),
+                   dbias_share_equal=bool(torch.equal(dg[1][1], dr[1][1])),
+                   dh_max_abs_diff=float((dg[0].float() - dr[0].float()).abs().max()))
+        doc["shapes"][name] = rec
+        print(f"W={W} {name}: gather {rec['gather']['median_ms']:.4f} ms (forward {rec['gather_forward']['median_ms']:.4f}), "
+              f"ring {rec['ring']['median_ms']:.4f} ms (forward {rec['ring_forward']['median_ms']:.4f}) (medians); "
+              f"ring/gather {rec['ring_over_gather']:.3f}; stage peak MiB gather {mem['gather'] / 2**20:.1f} ring "
+              f"{mem['ring'] / 2**20:.1f}; with rows gather {rec['rank_peak_bytes_gather'] / 2**20:.1f} ring "
+              f"{rec['rank_peak_bytes_ring'] / 2**20:.1f}; loss share equal {rec['loss_share_equal']}, dbias share equal "
+              f"{rec['dbias_share_equal']}", flush=True)
+        del zq_all, hs, plans, slots, dg, dr, arms
+        torch.cuda.empty_cache()
+    return doc
+
+
 def memory_record(dev):
     """torch.cuda.max_memory_allocated delta of one emulated rank's step (prep into its slot, forward,
     backward) at W = 2, n = 1024, d = 512, fp16, beside zq_all: the sigmoid loss and InfoNCE."""
@@ -218,6 +298,8 @@ def main(argv=None):
                     "sigmoid_cost_wW.json with --world, memory.json with --memory)")
     ap.add_argument("--world", type=int, default=1,
                     help="W > 1: one virtual rank of the distributed form against device-filled gathered rows")
+    ap.add_argument("--exchange", choices=["gather", "ring"], default="gather",
+                    help="with --world: ring times the ring stage ops beside the gather ones in alternating rounds")
     ap.add_argument("--memory", action="store_true", help="record one emulated rank's peak memory (W = 2) instead")
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
@@ -228,6 +310,11 @@ def main(argv=None):
     import ntxent_amd
 
     dev = torch.device("cuda", 0)
+    if args.exchange == "ring":
+        if args.memory or args.world < 2:
+            raise SystemExit("sigmoid_cost: --exchange ring goes with --world W, W > 1")
+        _write(ring_cost(args, dev), args.out or ROOT / "profiles" / "sigmoid_ring" / f"sigmoid_cost_w{args.world}.json")
+        return
     if args.memory or args.world > 1:
         name = "memory.json" if args.memory else f"sigmoid_cost_w{args.world}.json"
         _write(memory_record(dev) if args.memory else world_cost(args, dev),
