@@ -543,44 +543,33 @@ void launch_xview_sigmoid_bias_grad(const float* bias_part, const float* grad_ou
 // then launch_xview_dist_zt / launch_xview_dist_dz per side, launch_norm_bwd (dot_out), and the fp64
 // shares of launch_tau_grad (scale 1 / (2 * 2N tau^2) over the local dots) and
 // launch_xview_sigmoid_bias_grad (sum / 2N).
-void launch_xview_sigmoid_dist_fwd(DType comp, const void* zq_all, const Geometry& g, float bias, int q_lo, int q_hi,
-                                   int q_skip, double* lpart, hipStream_t stream, const float* pos_cos = nullptr);
-void launch_xview_sigmoid_dist_loss(const double* lpart, const Geometry& g, double* share, hipStream_t stream);
-void launch_xview_sigmoid_dist_coef(DType comp, const void* zq_all, const Geometry& g, float bias, int side, void* coef,
-                                    float* bias_part, hipStream_t stream, const float* pos_cos = nullptr);
-
-// Block form of the same, for an exchange that hands a rank ONE other rank's rows at a time (the ring):
-// zq [Rpad][ld_k] is this rank's own slot, rows_q a buffer of the same shape that holds rank q's rows
-// (q == g.rank: zq itself). q is the slot's identity (own block, positives, output place), not a
-// buffer index. A stage reads up to local row n + n_pad of either buffer: pass whole slots. No buffer
-// below has a size that depends on g.world, except lpart and bias_part (nT * W * nT entries).
-//   launch_xview_sigmoid_block_fwd : the nT x nT tiles of a_r against b_q; tile (I, Jl) writes
-//     lpart[(I * W + q) * nT + Jl], the gather launch's place. After all W blocks (any order)
-//     launch_xview_sigmoid_dist_loss gives the share, bitwise the gather path's. pos_cos is taken for
-//     q == g.rank only.
-//   launch_xview_sigmoid_block_coef: ONE side of the block, C = 2 G as planes [planes][n_pad][n_pad]
-//     (xview_block_coef_bytes; ldg = n_pad elements; planes as launch_xview_coef; exact zeros outside
-//     the valid rows and columns). Side 1 swaps the operand roles: rows b_r against a_q, the rows of
-//     this block of C^T. bias_part with side 0 and only there, at ((I * W + q) * nT + Jl) * 4 + wave,
-//     the gather launch's place: launch_xview_sigmoid_bias_grad after all W blocks is bitwise the
-//     gather path's share.
-//   launch_xview_block_zt : zt [2][En][n_pad] (xview_block_zt_bytes): both views of rows_q transposed,
-//     zero padded by index.
-//   launch_xview_block_dz : rows [side * n, side * n + n) of the fp32 slab dz [Rpad][dim_n], K = n_pad
-//     per plane (the residual plane, the rescale, the hi plane). accumulate false: stored (the first
-//     block; the slab needs no memset); true: dz = dz + product with plain loads and stores. One
-//     workgroup owns an element per launch and the launches are stream-ordered: deterministic in the
-//     order of the blocks, no atomics.
+//
+// Block form of the two, for an exchange that hands a rank ONE other rank's rows at a time (the ring):
+// rows_q not null. zq [Rpad][ld_k] is then this rank's own slot alone, rows_q a buffer of the same shape
+// that holds rank q's rows (q == g.rank: zq itself). q is the slot's identity (own block, positives,
+// output place), not a buffer index. A stage reads up to local row n + n_pad of either buffer: pass
+// whole slots. No buffer of the block form has a size that depends on g.world, except lpart and
+// bias_part (nT * W * nT entries).
+//   launch_xview_sigmoid_dist_fwd, [q_lo, q_hi) = [q, q + 1), q_skip -1: the nT x nT tiles of a_r against
+//     b_q; tile (I, Jl) writes lpart[(I * W + q) * nT + Jl], the gather launch's place. After all W
+//     blocks (any order) launch_xview_sigmoid_dist_loss gives the share, bitwise the gather path's.
+//     pos_cos is taken for q == g.rank only.
+//   launch_xview_sigmoid_dist_coef (q is read only here): ONE side of the block, C = 2 G as planes
+//     [planes][n_pad][n_pad] (xview_block_coef_bytes; ldg = n_pad elements; planes as launch_xview_coef;
+//     exact zeros outside the valid rows and columns). Side 1 swaps the operand roles: rows b_r against
+//     a_q, the rows of this block of C^T. bias_part with side 0 and only there, at
+//     ((I * W + q) * nT + Jl) * 4 + wave, the gather launch's place: launch_xview_sigmoid_bias_grad after
+//     all W blocks is bitwise the gather path's share.
+// then launch_xview_dist_zt / launch_xview_dist_dz with kslots = 1 (xview_block_zt_bytes).
 size_t xview_block_coef_bytes(DType comp, const Geometry& g);
 size_t xview_block_zt_bytes(DType comp, const Geometry& g);
-void launch_xview_sigmoid_block_fwd(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias, int q,
-                                    double* lpart, hipStream_t stream, const float* pos_cos = nullptr);
-void launch_xview_sigmoid_block_coef(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
-                                     int q, int side, void* coef, float* bias_part, hipStream_t stream,
-                                     const float* pos_cos = nullptr);
-void launch_xview_block_zt(DType comp, const void* rows_q, const Geometry& g, void* zt, hipStream_t stream);
-void launch_xview_block_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
-                           bool accumulate, hipStream_t stream);
+void launch_xview_sigmoid_dist_fwd(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
+                                   int q_lo, int q_hi, int q_skip, double* lpart, hipStream_t stream,
+                                   const float* pos_cos = nullptr);
+void launch_xview_sigmoid_dist_loss(const double* lpart, const Geometry& g, double* share, hipStream_t stream);
+void launch_xview_sigmoid_dist_coef(DType comp, const void* zq, const void* rows_q, int q, const Geometry& g, float bias,
+                                    int side, void* coef, float* bias_part, hipStream_t stream,
+                                    const float* pos_cos = nullptr);
 
 // ---- distributed cross-view InfoNCE: rank g.rank of g.world ranks ---------------------------------
 // The global-batch form of the loss above. Every rank holds n = R/2 pairs; the global batch in pair
@@ -599,15 +588,19 @@ void launch_xview_block_dz(DType comp, const void* coef, const void* zt, const G
 //     rank's share sum_i (lse_i - y_ip) / (2N), in fp64: a SUM over the ranks, rounded to fp32 once,
 //     gives the loss (fp32 shares would round W + 1 times, more than the one-GPU loss does). scratch:
 //     xview_lse_scratch_bytes (8-byte aligned, no initialisation needed).
-//   launch_xview_dist_zt  : zt [2][En][W * n_pad] (xview_zt_bytes): view v of slot q transposed
-//     into columns [q * n_pad, (q + 1) * n_pad), zero padded.
+//   launch_xview_dist_zt  : zt [2][En][kslots * n_pad] (xview_zt_bytes): view v of slot q of `rows`
+//     transposed into columns [q * n_pad, (q + 1) * n_pad), zero padded by index. kslots: g.world (the
+//     gathered rows), or 1: `rows` is one slot, any rank's (xview_block_zt_bytes).
 //   launch_xview_dist_coef: the n_pad x W n_pad coefficient block of ONE side,
 //     G_ij = exp2(y_ij - lse2_i) + exp2(y_ij - lse2_j) - 2 [j = p(i)], into `coef`
 //     (xview_coef_bytes = 4 n_pad W n_pad bytes in every plan; planes as launch_xview_coef),
 //     exact zeros outside the valid rows and columns.
 //   launch_xview_dist_dz  : rows [side * n, side * n + n) of the fp32 slab dz [Rpad][dim_n]
-//     (xview_dz_bytes) = G Z over K = planes x W x n_pad (xview_dz_kernel: the residual plane, then
-//     the hi plane, the rank slots ascending inside each).
+//     (xview_dz_bytes) = G Z over K = planes x kslots x n_pad (xview_dz_kernel: the residual plane,
+//     the rescale, the hi plane, the rank slots ascending inside each); kslots as the coef and zt it
+//     reads were made with. accumulate false: stored (the slab needs no memset); true (a later block
+//     of the ring): dz = dz + product with plain loads and stores. One workgroup owns an element per
+//     launch and the launches are stream-ordered: deterministic in the order of the blocks, no atomics.
 // Side 0 then side 1 through the same `coef`, then launch_norm_bwd (whose scale is the global
 // 1 / (2N tau)). No atomics, no host sync: deterministic and capturable. The same kernels as above
 // (one GPU is W = 1 of them, with the column partials and the in-place G^T in place of side 1); the
@@ -616,11 +609,11 @@ void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, in
                            float2* part, float* ypos, hipStream_t stream);
 void launch_xview_dist_lse(const float2* part, const float* ypos, const Geometry& g, float* lse2_all, float* cpos,
                            double* loss, void* scratch, hipStream_t stream);
-void launch_xview_dist_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream);
+void launch_xview_dist_zt(DType comp, const void* rows, const Geometry& g, int kslots, void* zt, hipStream_t stream);
 void launch_xview_dist_coef(DType comp, const void* zq_all, const float* lse2_all, const float* cpos,
                             const Geometry& g, int side, void* coef, hipStream_t stream);
-void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
-                          hipStream_t stream);
+void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int kslots, int side,
+                          float* dz, bool accumulate, hipStream_t stream);
 
 // ---- device utilities (reference utils::get_optimal_block_size / check_tensor_core_support
 //      at include/ntxent_kernel.cuh:80-110) ------------------------------------------------

@@ -61,7 +61,8 @@
 // GPU is W = 1, side 0 of both, with the in-place transpose in place of side 1.
 // The block form of both epilogues (kBlock) and of the dZ product (kAccum) serves the ring exchange:
 // this rank's one slot against one other rank's slot at a time, the same arithmetic, the partials at
-// the gather launches' places and the dZ slab accumulated block after block (launch_xview_*_block_*).
+// the gather launches' places and the dZ slab accumulated block after block (the rows_q / kslots = 1
+// forms of launch_xview_sigmoid_dist_* and launch_xview_dist_zt / _dz).
 #include "../include/ntxent/ntxent.h"
 #include "device_common.h"
 #include "host_common.h"
@@ -778,25 +779,40 @@ void xv_lse_loss(const float2* part, const float* ypos, const Geometry& g, float
                      (double)g.global_rows, loss, share64);
 }
 
-void xv_launch_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream) {
+// The slots [q_lo, q_hi) except q_skip (-1: none) as a forward launch's columns.
+void xv_slot_range(dev::XvParams& p, const Geometry& g, int q_lo, int q_hi, int q_skip, const std::string& who) {
+  NTXENT_CHECK(0 <= q_lo && q_lo <= q_hi && q_hi <= g.world && q_skip < q_hi && (q_skip < 0 || q_skip >= q_lo),
+               who + ": bad slot range");
+  p.q_lo = q_lo;
+  p.nq = q_hi - q_lo - (q_skip >= 0 ? 1 : 0);
+  p.q_skip = q_skip;
+}
+
+// kslots: the rank slots that `rows` holds and zt gets side by side, g.world, or 1 (blockIdx.z = v
+// then, so the slot strides are never applied).
+void xv_launch_zt(DType comp, const void* rows, const Geometry& g, int kslots, void* zt, hipStream_t stream) {
   const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
   dispatch_comp(comp, [&](auto tc) {
     using Tc = decltype(tc);
-    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2 * g.world), dim3(256), 0, stream,
-                       static_cast<const Tc*>(zq_all), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
-                       (long long)g.world * np, (long long)g.rows_pad, (long long)np);
+    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2 * kslots), dim3(256), 0, stream,
+                       static_cast<const Tc*>(rows), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
+                       (long long)kslots * np, (long long)g.rows_pad, (long long)np);
   });
+}
+
+// One side's coefficient block in coef: planes of n_pad rows, kslots * n_pad columns.
+void xv_coef_planes(DType comp, const Geometry& g, int kslots, void* coef, dev::XvParams& p) {
+  p.gbuf = static_cast<char*>(coef);
+  p.ldg = (long long)kslots * xv_npad(g) * (long long)dtype_size(comp);
+  p.plane_bytes = (long long)xv_npad(g) * p.ldg;
 }
 
 void xv_launch_coef(DType comp, dev::XvParams p, const Geometry& g, int side, const float* lse2_all,
                     const float* cpos, void* coef, hipStream_t stream) {
-  const int np = xv_npad(g);
   p.side = side;
   p.lse2 = lse2_all;
   p.cpos = cpos;
-  p.gbuf = static_cast<char*>(coef);
-  p.ldg = (long long)g.world * np * (long long)dtype_size(comp);
-  p.plane_bytes = (long long)np * p.ldg;
+  xv_coef_planes(comp, g, g.world, coef, p);
   const int ntiles = p.nT * g.world * p.nT;
   dispatch_comp(comp, [&](auto tc) {
     hipLaunchKernelGGL((dev::xview_side_coef_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
@@ -866,7 +882,7 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
                        void* zt, hipStream_t stream) {
   NTXENT_CHECK(zq && lse2 && cpos && coef && zt, "xview_coef: null buffer");
   const dev::XvParams p = xv_params_one(comp, zq, g, "xview_coef");
-  xv_launch_zt(comp, zq, g, zt, stream);
+  xv_launch_zt(comp, zq, g, g.world, zt, stream);
   xv_launch_coef(comp, p, g, 0, lse2, cpos, coef, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
@@ -893,13 +909,19 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
 
 // ---- pairwise sigmoid loss -----------------------------------------------------------------------------
 namespace {
-// one: the one-GPU launches' geometry checks (world 1, rows padded to 256)
-dev::XvSigParams xv_sig_params(DType comp, const void* zq, const Geometry& g, float bias, const std::string& who,
-                               bool one = true) {
+// Rank g.rank's tiles against the rank slots [q_lo, q_hi) except q_skip. rows_q null: the slots are
+// zq's, every rank's rows (one: the one-GPU launches' geometry checks, world 1, rows padded to 256).
+// Otherwise the block form: zq is the own slot alone and rows_q holds the rows of slot q_lo, the only one.
+dev::XvSigParams xv_sig_params(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias, int q_lo,
+                               int q_hi, int q_skip, const float* pos_cos, const std::string& who, bool one = false) {
   dev::XvSigParams ps{};
   ps.x = one ? xv_params_one(comp, zq, g, who) : xv_params(comp, zq, g, who);
+  xv_slot_range(ps.x, g, q_lo, q_hi, q_skip, who);
+  NTXENT_CHECK(!rows_q || ps.x.nq == 1, who + ": a block is one slot");
+  ps.x.zcol = static_cast<const char*>(rows_q);
   ps.scale2 = (double)g.inv_temp * 1.4426950408889634;
   ps.bias2 = (double)bias * 1.4426950408889634;
+  ps.pos_cos = rows_q && q_lo != g.rank ? nullptr : pos_cos;  // the own block alone holds positives
   return ps;
 }
 // side 0's tiles of a rank: nT row tiles x world * nT column tiles
@@ -907,24 +929,33 @@ inline size_t xv_sig_tiles(const Geometry& g) {
   const size_t nT = (size_t)(xv_npad(g) / dev::kXvTile);
   return nT * (size_t)g.world * nT;
 }
-void xv_sig_launch_fwd(DType comp, const dev::XvSigParams& ps, hipStream_t stream) {
-  const int ntiles = ps.x.nT * ps.x.nq * ps.x.nT;
+// block: the kBlock form (the columns are ps.x.zcol's rows)
+void xv_sig_launch_fwd(DType comp, dev::XvSigParams ps, double* lpart, bool block, hipStream_t stream) {
+  ps.lpart = lpart;
+  const dim3 grid(ps.x.nT * ps.x.nq * ps.x.nT);
   dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, ps);
+    using Tc = decltype(tc);
+    if (!block) {
+      hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, ps);
+    } else {
+      hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<Tc, true>), grid, dim3(dev::kXvThreads), 0, stream, ps);
+    }
   });
 }
-// one side's block into coef: planes of n_pad rows, world * n_pad columns (xv_launch_coef's layout)
+// one side's block against ps's slots into coef (xv_coef_planes); bias_part with side 0 and only there
 void xv_sig_launch_coef(DType comp, dev::XvSigParams ps, const Geometry& g, int side, void* coef, float* bias_part,
-                        hipStream_t stream) {
-  const int np = xv_npad(g);
+                        bool block, hipStream_t stream) {
   ps.x.side = side;
-  ps.x.gbuf = static_cast<char*>(coef);
-  ps.x.ldg = (long long)g.world * np * (long long)dtype_size(comp);
-  ps.x.plane_bytes = (long long)np * ps.x.ldg;
+  xv_coef_planes(comp, g, ps.x.nq, coef, ps.x);
   ps.bias_part = bias_part;
+  const dim3 grid(ps.x.nT * ps.x.nq * ps.x.nT);
   dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<decltype(tc)>), dim3((int)xv_sig_tiles(g)), dim3(dev::kXvThreads), 0,
-                       stream, ps);
+    using Tc = decltype(tc);
+    if (!block) {
+      hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, ps);
+    } else {
+      hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<Tc, true>), grid, dim3(dev::kXvThreads), 0, stream, ps);
+    }
   });
 }
 }  // namespace
@@ -948,23 +979,21 @@ void launch_xview_sigmoid_pos(DType in, const void* h, const float* inv, const G
 void launch_xview_sigmoid_fwd(DType comp, const void* zq, const Geometry& g, float bias, float* loss, void* scratch,
                               hipStream_t stream, const float* pos_cos) {
   NTXENT_CHECK(zq && loss && scratch, "xview_sigmoid_fwd: null buffer");
-  dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, "xview_sigmoid_fwd");
-  ps.pos_cos = pos_cos;
-  ps.lpart = static_cast<double*>(scratch);
-  xv_sig_launch_fwd(comp, ps, stream);
+  double* lpart = static_cast<double*>(scratch);
+  xv_sig_launch_fwd(comp, xv_sig_params(comp, zq, nullptr, g, bias, 0, 1, -1, pos_cos, "xview_sigmoid_fwd", true), lpart,
+                    false, stream);
   // the tiles' partials in a fixed order, over the n pairs
-  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, ps.lpart,
-                     (int)xv_sig_tiles(g), (double)(g.rows / 2), loss, nullptr);
+  hipLaunchKernelGGL(dev::xview_loss_kernel, dim3(1), dim3(dev::kXvSumThreads), 0, stream, lpart, (int)xv_sig_tiles(g),
+                     (double)(g.rows / 2), loss, nullptr);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
 void launch_xview_sigmoid_coef(DType comp, const void* zq, const Geometry& g, float bias, void* coef, void* zt,
                                float* bias_part, hipStream_t stream, const float* pos_cos) {
   NTXENT_CHECK(zq && coef && zt && bias_part, "xview_sigmoid_coef: null buffer");
-  dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, "xview_sigmoid_coef");
-  ps.pos_cos = pos_cos;
-  xv_launch_zt(comp, zq, g, zt, stream);
-  xv_sig_launch_coef(comp, ps, g, 0, coef, bias_part, stream);
+  const dev::XvSigParams ps = xv_sig_params(comp, zq, nullptr, g, bias, 0, 1, -1, pos_cos, "xview_sigmoid_coef", true);
+  xv_launch_zt(comp, zq, g, g.world, zt, stream);
+  xv_sig_launch_coef(comp, ps, g, 0, coef, bias_part, false, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -978,20 +1007,21 @@ void launch_xview_sigmoid_bias_grad(const float* bias_part, const float* grad_ou
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-// rank g.rank of g.world
-void launch_xview_sigmoid_dist_fwd(DType comp, const void* zq_all, const Geometry& g, float bias, int q_lo, int q_hi,
-                                   int q_skip, double* lpart, hipStream_t stream, const float* pos_cos) {
-  NTXENT_CHECK(zq_all && lpart, "xview_sigmoid_dist_fwd: null buffer");
-  NTXENT_CHECK(0 <= q_lo && q_lo <= q_hi && q_hi <= g.world && q_skip < q_hi && (q_skip < 0 || q_skip >= q_lo),
-               "xview_sigmoid_dist_fwd: bad slot range");
-  dev::XvSigParams ps = xv_sig_params(comp, zq_all, g, bias, "xview_sigmoid_dist_fwd", false);
-  ps.x.q_lo = q_lo;
-  ps.x.nq = q_hi - q_lo - (q_skip >= 0 ? 1 : 0);
-  ps.x.q_skip = q_skip;
-  ps.pos_cos = pos_cos;
-  ps.lpart = lpart;
+// ---- rank g.rank of g.world: every slot gathered in zq (rows_q null, kslots = g.world), or the block
+// form, ONE rank slot at a time (the ring exchange; rows_q, kslots = 1) ------------------------------------
+// Block form: zq is this rank's own slot [rows_pad][ld_k]; rows_q a buffer of the same shape that holds
+// rank q's rows (q == g.rank: zq itself). Every row a stage can read, up to local row n + n_pad <=
+// rows_pad, lies in the one slot: the buffers must be whole slots (received whole, or zero beyond what
+// was received). Nothing there has a size that depends on g.world except lpart / bias_part, which keep
+// the gather launches' layout so that the same two sums finish the loss and dL/dbias.
+void launch_xview_sigmoid_dist_fwd(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
+                                   int q_lo, int q_hi, int q_skip, double* lpart, hipStream_t stream,
+                                   const float* pos_cos) {
+  NTXENT_CHECK(zq && lpart, "xview_sigmoid_dist_fwd: null buffer");
+  const dev::XvSigParams ps =
+      xv_sig_params(comp, zq, rows_q, g, bias, q_lo, q_hi, q_skip, pos_cos, "xview_sigmoid_dist_fwd");
   if (ps.x.nq == 0) return;
-  xv_sig_launch_fwd(comp, ps, stream);
+  xv_sig_launch_fwd(comp, ps, lpart, rows_q != nullptr, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -1002,26 +1032,21 @@ void launch_xview_sigmoid_dist_loss(const double* lpart, const Geometry& g, doub
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-void launch_xview_sigmoid_dist_coef(DType comp, const void* zq_all, const Geometry& g, float bias, int side, void* coef,
-                                    float* bias_part, hipStream_t stream, const float* pos_cos) {
-  NTXENT_CHECK(zq_all && coef && (side == 0 || side == 1), "xview_sigmoid_dist_coef: bad argument");
+void launch_xview_sigmoid_dist_coef(DType comp, const void* zq, const void* rows_q, int q, const Geometry& g, float bias,
+                                    int side, void* coef, float* bias_part, hipStream_t stream, const float* pos_cos) {
+  NTXENT_CHECK(zq && coef && (side == 0 || side == 1), "xview_sigmoid_dist_coef: bad argument");
   NTXENT_CHECK((side == 0) == (bias_part != nullptr), "xview_sigmoid_dist_coef: bias_part with side 0 and only there");
-  dev::XvSigParams ps = xv_sig_params(comp, zq_all, g, bias, "xview_sigmoid_dist_coef", false);
-  ps.pos_cos = pos_cos;
-  xv_sig_launch_coef(comp, ps, g, side, coef, bias_part, stream);
+  const dev::XvSigParams ps = xv_sig_params(comp, zq, rows_q, g, bias, rows_q ? q : 0, rows_q ? q + 1 : g.world, -1,
+                                            pos_cos, "xview_sigmoid_dist_coef");
+  xv_sig_launch_coef(comp, ps, g, side, coef, bias_part, rows_q != nullptr, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-// ---- rank g.rank of g.world ------------------------------------------------------------------------------
 void launch_xview_dist_fwd(DType comp, const void* zq_all, const Geometry& g, int q_lo, int q_hi, int q_skip,
                            float2* part, float* ypos, hipStream_t stream) {
   NTXENT_CHECK(zq_all && part && ypos, "xview_dist_fwd: null buffer");
-  NTXENT_CHECK(0 <= q_lo && q_lo <= q_hi && q_hi <= g.world && q_skip < q_hi && (q_skip < 0 || q_skip >= q_lo),
-               "xview_dist_fwd: bad slot range");
   dev::XvParams p = xv_params(comp, zq_all, g, "xview_dist_fwd");
-  p.q_lo = q_lo;
-  p.nq = q_hi - q_lo - (q_skip >= 0 ? 1 : 0);
-  p.q_skip = q_skip;
+  xv_slot_range(p, g, q_lo, q_hi, q_skip, "xview_dist_fwd");
   p.part = part;
   p.ypos = ypos;
   if (p.nq == 0) return;
@@ -1039,10 +1064,10 @@ void launch_xview_dist_lse(const float2* part, const float* ypos, const Geometry
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-void launch_xview_dist_zt(DType comp, const void* zq_all, const Geometry& g, void* zt, hipStream_t stream) {
-  NTXENT_CHECK(zq_all && zt, "xview_dist_zt: null buffer");
-  xv_params(comp, zq_all, g, "xview_dist_zt");
-  xv_launch_zt(comp, zq_all, g, zt, stream);
+void launch_xview_dist_zt(DType comp, const void* rows, const Geometry& g, int kslots, void* zt, hipStream_t stream) {
+  NTXENT_CHECK(rows && zt && (kslots == g.world || kslots == 1), "xview_dist_zt: bad argument");
+  xv_params(comp, rows, g, "xview_dist_zt");
+  xv_launch_zt(comp, rows, g, kslots, zt, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -1053,96 +1078,12 @@ void launch_xview_dist_coef(DType comp, const void* zq_all, const float* lse2_al
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
-void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
-                          hipStream_t stream) {
-  NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1), "xview_dist_dz: bad argument");
+void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int kslots, int side,
+                          float* dz, bool accumulate, hipStream_t stream) {
+  NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1) && (kslots == g.world || kslots == 1),
+               "xview_dist_dz: bad argument");
   xv_params(comp, nullptr, g, "xview_dist_dz");
-  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dist_dz", g.world);
-  q.side = side;
-  const dim3 grid(q.En / dev::kXvTile, xv_npad(g) / dev::kXvTile);
-  dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_dz_kernel<decltype(tc)>), grid, dim3(dev::kXvThreads), 0, stream, q);
-  });
-  NTXENT_HIP_CHECK(hipGetLastError());
-}
-
-// ---- block form: rank g.rank against ONE rank slot at a time (the ring exchange) -----------------------
-// zq: this rank's own slot [rows_pad][ld_k]; rows_q: a buffer of the same shape that holds rank q's rows
-// (q == g.rank: zq itself). Every row a stage can read, up to local row n + n_pad <= rows_pad, lies in
-// the one slot: the buffers must be whole slots (received whole, or zero beyond what was received).
-// Nothing here has a size that depends on g.world except lpart / bias_part, which keep the gather
-// launches' layout so that the same two sums finish the loss and dL/dbias.
-namespace {
-dev::XvSigParams xv_sig_block_params(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
-                                     int q, const std::string& who) {
-  NTXENT_CHECK(0 <= q && q < g.world, who + ": slot q outside the world");
-  dev::XvSigParams ps = xv_sig_params(comp, zq, g, bias, who, false);
-  ps.x.zcol = static_cast<const char*>(rows_q);
-  ps.x.q_lo = q;
-  ps.x.nq = 1;
-  ps.x.q_skip = -1;
-  return ps;
-}
-}  // namespace
-
-size_t xview_block_coef_bytes(DType comp, const Geometry& g) {
-  return (size_t)xv_planes(comp) * xv_npad(g) * xv_npad(g) * dtype_size(comp);
-}
-size_t xview_block_zt_bytes(DType comp, const Geometry& g) {
-  return (size_t)2 * xv_en(g) * xv_npad(g) * dtype_size(comp);
-}
-
-void launch_xview_sigmoid_block_fwd(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias, int q,
-                                    double* lpart, hipStream_t stream, const float* pos_cos) {
-  NTXENT_CHECK(zq && rows_q && lpart, "xview_sigmoid_block_fwd: null buffer");
-  dev::XvSigParams ps = xv_sig_block_params(comp, zq, rows_q, g, bias, q, "xview_sigmoid_block_fwd");
-  ps.pos_cos = q == g.rank ? pos_cos : nullptr;  // the own block alone holds positives
-  ps.lpart = lpart;
-  dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc), true>), dim3(ps.x.nT * ps.x.nT), dim3(dev::kXvThreads),
-                       0, stream, ps);
-  });
-  NTXENT_HIP_CHECK(hipGetLastError());
-}
-
-void launch_xview_sigmoid_block_coef(DType comp, const void* zq, const void* rows_q, const Geometry& g, float bias,
-                                     int q, int side, void* coef, float* bias_part, hipStream_t stream,
-                                     const float* pos_cos) {
-  NTXENT_CHECK(zq && rows_q && coef && (side == 0 || side == 1), "xview_sigmoid_block_coef: bad argument");
-  NTXENT_CHECK((side == 0) == (bias_part != nullptr), "xview_sigmoid_block_coef: bias_part with side 0 and only there");
-  dev::XvSigParams ps = xv_sig_block_params(comp, zq, rows_q, g, bias, q, "xview_sigmoid_block_coef");
-  ps.pos_cos = q == g.rank ? pos_cos : nullptr;
-  ps.x.side = side;
-  ps.x.gbuf = static_cast<char*>(coef);
-  ps.x.ldg = (long long)xv_npad(g) * (long long)dtype_size(comp);
-  ps.x.plane_bytes = (long long)xv_npad(g) * ps.x.ldg;
-  ps.bias_part = bias_part;
-  dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<decltype(tc), true>), dim3(ps.x.nT * ps.x.nT), dim3(dev::kXvThreads),
-                       0, stream, ps);
-  });
-  NTXENT_HIP_CHECK(hipGetLastError());
-}
-
-void launch_xview_block_zt(DType comp, const void* rows_q, const Geometry& g, void* zt, hipStream_t stream) {
-  NTXENT_CHECK(rows_q && zt, "xview_block_zt: null buffer");
-  xv_params(comp, rows_q, g, "xview_block_zt");
-  const int np = xv_npad(g), en = xv_en(g), n = g.rows / 2;
-  // one slot: blockIdx.z = v, so the slot strides are never applied
-  dispatch_comp(comp, [&](auto tc) {
-    using Tc = decltype(tc);
-    hipLaunchKernelGGL((dev::xview_transpose_kernel<Tc>), dim3(np / 64, en / 64, 2), dim3(256), 0, stream,
-                       static_cast<const Tc*>(rows_q), static_cast<Tc*>(zt), n, g.dim_k, (long long)g.ld_k, en,
-                       (long long)np, (long long)g.rows_pad, (long long)np);
-  });
-  NTXENT_HIP_CHECK(hipGetLastError());
-}
-
-void launch_xview_block_dz(DType comp, const void* coef, const void* zt, const Geometry& g, int side, float* dz,
-                           bool accumulate, hipStream_t stream) {
-  NTXENT_CHECK(coef && zt && dz && (side == 0 || side == 1), "xview_block_dz: bad argument");
-  xv_params(comp, nullptr, g, "xview_block_dz");
-  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_block_dz", 1);
+  dev::XvDzParams q = xv_dz_params(comp, coef, zt, g, dz, "xview_dist_dz", kslots);
   q.side = side;
   const dim3 grid(q.En / dev::kXvTile, xv_npad(g) / dev::kXvTile);
   dispatch_comp(comp, [&](auto tc) {
@@ -1154,6 +1095,13 @@ void launch_xview_block_dz(DType comp, const void* coef, const void* zt, const G
     }
   });
   NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+size_t xview_block_coef_bytes(DType comp, const Geometry& g) {
+  return (size_t)xv_planes(comp) * xv_npad(g) * xv_npad(g) * dtype_size(comp);
+}
+size_t xview_block_zt_bytes(DType comp, const Geometry& g) {
+  return (size_t)2 * xv_en(g) * xv_npad(g) * dtype_size(comp);
 }
 
 }  // namespace ntxent

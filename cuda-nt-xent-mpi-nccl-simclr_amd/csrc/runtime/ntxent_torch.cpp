@@ -184,6 +184,17 @@ static void check_stacked(const at::Tensor& h, const std::string& name = "h") {
   NTXENT_CHECK(h.size(0) > 0 && h.size(0) % 2 == 0, name + " must hold an even number of rows (two stacked views)");
 }
 
+// this rank's input rows [rows, dim] of the plan's geometry
+static void check_h(const at::Tensor& h, const Geometry& g) {
+  check_input(h, "h");
+  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
+}
+
+// prep's inv of those rows
+static void check_inv(const at::Tensor& inv, const Geometry& g) {
+  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows] (prep's output)");
+}
+
 // the first element of the incoming gradient as a contiguous fp32 [1] tensor on its device
 static at::Tensor grad_scalar(const at::Tensor& grad_out) {
   return grad_out.to(at::kFloat).reshape({-1}).narrow(0, 0, 1).contiguous();
@@ -230,8 +241,7 @@ static GemmWorkspace gemm_ws(const at::Tensor& like, int ntiles, const Plan& P, 
 // only for fp8 plans (undefined otherwise), written into `zq8_out` when given.
 std::vector<at::Tensor> prep(const at::Tensor& h, const Plan& P, const c10::optional<at::Tensor>& zq_out,
                              const c10::optional<at::Tensor>& zq8_out) {
-  check_input(h, "h");
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == P.g.rows && h.size(1) == P.g.dim, "h shape does not match plan");
+  check_h(h, P.g);
   const at::DeviceGuard guard(h.device());
   at::Tensor zq;
   if (zq_out.has_value() && zq_out->defined()) {
@@ -331,13 +341,12 @@ static void check_xview_saved(const at::Tensor& inv, const at::Tensor& lse2_all,
   check_xview_stats(lse2_all, cpos, g, msg);
 }
 
-// The end of both backwards: coef and zt are released before dh exists, then the grad_out / (2N tau)
-// scaling and the normalisation backward of the slab; dot: also dot_i = z_i . (C z)_i, [rows].
+// The end of every backward (the callers release coef and zt before it: before dh exists): the
+// grad_out / (2N tau) scaling and the normalisation backward of the slab; dot: also
+// dot_i = z_i . (C z)_i, [rows].
 static at::Tensor xview_backward_tail(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& go,
-                                      const at::Tensor& dz, at::Tensor& coef, at::Tensor& zt, const Geometry& g,
-                                      hipStream_t stream, at::Tensor* dot = nullptr) {
-  coef.reset();
-  zt.reset();
+                                      const at::Tensor& dz, const Geometry& g, hipStream_t stream,
+                                      at::Tensor* dot = nullptr) {
   auto dh = at::empty_like(h);
   if (dot) *dot = at::empty({g.rows}, opts(h, at::kFloat));
   launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
@@ -345,69 +354,9 @@ static at::Tensor xview_backward_tail(const at::Tensor& h, const at::Tensor& inv
   return dh;
 }
 
-// want_tau: also dL/dtau times grad_out, a 0-d fp32 tensor; undefined otherwise. compute: the
-// forward's.
-static std::pair<at::Tensor, at::Tensor> xview_backward_impl(const at::Tensor& h, const at::Tensor& inv,
-                                                             const at::Tensor& lse2, const at::Tensor& cpos,
-                                                             const at::Tensor& grad_out, double T,
-                                                             const std::string& compute, bool want_tau) {
-  check_input(h, "h");
-  const at::DeviceGuard guard(h.device());
-  const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
-  auto P = xview_plan(h, T, comp);
-  const Geometry& g = P->g;
-  check_xview_saved(inv, lse2, cpos, g,
-                    "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
-  const hipStream_t stream = cur_stream(h);
-  auto go = grad_scalar(grad_out);
-  // buffers live only as long as a stage needs them (stream-ordered reuse by the allocator): the
-  // unit rows until the coefficients exist, coefficients and transposes until the slab exists
-  auto coef = at::empty({(long)xview_coef_bytes(comp, g)}, opts(h, at::kByte));
-  auto zt = at::empty({(long)xview_zt_bytes(comp, g)}, opts(h, at::kByte));
-  {
-    // The row prologue runs a second time (a seventh launch and a second read of h) so that zq need
-    // not be saved across the step. REQUIREMENT on launch_prep: for the same h, plan and device it
-    // must reproduce the forward's zq bit for bit (no atomics, no launch-dependent summation order),
-    // because the saved lse2 / cpos were formed from the forward's zq and the coefficients
-    // exp2(cos - lse2) are formed from this one; a prologue that is not repeatable would make G
-    // inconsistent with its own normaliser. test_gpu_infonce.py::test_prep_is_bitwise_repeatable
-    // holds it to that.
-    const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
-    launch_xview_coef(comp, st[0].data_ptr(), lse2.data_ptr<float>(), cpos.data_ptr<float>(), g, coef.data_ptr(),
-                      zt.data_ptr(), stream);
-  }
-  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
-  launch_xview_dz(comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
-  at::Tensor dot, dtau;
-  auto dh = xview_backward_tail(h, inv, go, dz, coef, zt, g, stream, &dot);
-  if (want_tau) {
-    dtau = at::empty({}, opts(h, at::kFloat));
-    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau.data_ptr<float>(), g, stream);
-  }
-  return {dh, dtau};
-}
-
-at::Tensor xview_backward(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& lse2, const at::Tensor& cpos,
-                          const at::Tensor& grad_out, double T, const std::string& compute) {
-  return xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, false).first;
-}
-
-// xview_backward plus the temperature gradient: (dh, dtau); dh is bitwise xview_backward's.
-std::tuple<at::Tensor, at::Tensor> xview_backward_tau(const at::Tensor& h, const at::Tensor& inv,
-                                                      const at::Tensor& lse2, const at::Tensor& cpos,
-                                                      const at::Tensor& grad_out, double T,
-                                                      const std::string& compute) {
-  auto r = xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, true);
-  return {r.first, r.second};
-}
-
-// ---- pairwise sigmoid loss, the SigLIP form (kernels/xview_kernels.hip) ----------------------------
-// Stacked views h = [h1; h2] on the current stream: the row prologue and the N x N tile GEMM with the
-// softplus epilogue. The compute dtype resolves as for xview_forward ("fp8" computes in fp16).
-// Returns {loss, inv}: nothing else needs saving (no normaliser; the backward runs the prologue again).
-// 16-bit plans: the pairs' cosines from the input rows in fp32 (launch_xview_sigmoid_pos), [R/2];
-// undefined for fp32 plans. The forward and the backward form them from the same h and inv: the
-// same bits.
+// 16-bit plans of the pairwise sigmoid loss: the pairs' cosines from the input rows in fp32
+// (launch_xview_sigmoid_pos), [R/2]; undefined for fp32 plans. The forward and the backward form them
+// from the same h and inv: the same bits.
 static at::Tensor sigmoid_pos_cos(const at::Tensor& h, const at::Tensor& inv, DType comp, const Geometry& g) {
   if (comp == DType::F32) return at::Tensor();
   auto pos = at::empty({g.rows / 2}, opts(h, at::kFloat));
@@ -416,6 +365,81 @@ static at::Tensor sigmoid_pos_cos(const at::Tensor& h, const at::Tensor& inv, DT
   return pos;
 }
 
+// The one-GPU backward of both losses, after the caller's checks: dh, and in *dtau (null: not wanted)
+// dL/dtau times grad_out, a 0-d fp32 tensor. launch_coef(zq, coef, zt, pos_cos, stream): the loss's
+// transposes and coefficient block. bias_part not null: the sigmoid loss. Its tiles' sums of C are
+// allocated here, after zt, and the pairs' cosines (sigmoid_pos_cos; null otherwise) live as long as
+// the unit rows.
+template <class LaunchCoef>
+static at::Tensor xview_backward_body(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& go, const Plan& P,
+                                      at::Tensor* bias_part, at::Tensor* dtau, LaunchCoef launch_coef) {
+  const Geometry& g = P.g;
+  const hipStream_t stream = cur_stream(h);
+  // buffers live only as long as a stage needs them (stream-ordered reuse by the allocator): the
+  // unit rows until the coefficients exist, coefficients and transposes until the slab exists
+  auto coef = at::empty({(long)xview_coef_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(h, at::kByte));
+  if (bias_part) *bias_part = at::empty({(long)(xview_sigmoid_bias_part_bytes(g) / 4)}, opts(h, at::kFloat));
+  {
+    // The row prologue runs a second time (a seventh launch and a second read of h) so that zq need
+    // not be saved across the step. REQUIREMENT on launch_prep: for the same h, plan and device it
+    // must reproduce the forward's zq bit for bit (no atomics, no launch-dependent summation order),
+    // because the saved lse2 / cpos were formed from the forward's zq and the coefficients
+    // exp2(cos - lse2) are formed from this one; a prologue that is not repeatable would make G
+    // inconsistent with its own normaliser. test_gpu_infonce.py::test_prep_is_bitwise_repeatable
+    // holds it to that.
+    const auto st = prep(h, P, c10::nullopt, c10::nullopt);
+    const at::Tensor pos = bias_part ? sigmoid_pos_cos(h, inv, P.comp, g) : at::Tensor();
+    launch_coef(st[0].data_ptr(), coef.data_ptr(), zt.data_ptr(), pos.defined() ? pos.data_ptr<float>() : nullptr, stream);
+  }
+  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
+  launch_xview_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
+  coef.reset();
+  zt.reset();
+  at::Tensor dot;
+  auto dh = xview_backward_tail(h, inv, go, dz, g, stream, &dot);
+  if (dtau) {
+    *dtau = at::empty({}, opts(h, at::kFloat));
+    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau->data_ptr<float>(), g, stream);
+  }
+  return dh;
+}
+
+// dtau as xview_backward_body's. compute: the forward's.
+static at::Tensor xview_backward_impl(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& lse2,
+                                      const at::Tensor& cpos, const at::Tensor& grad_out, double T,
+                                      const std::string& compute, at::Tensor* dtau) {
+  check_input(h, "h");
+  const at::DeviceGuard guard(h.device());
+  auto P = xview_plan(h, T, backward_dtype(choose_compute(h.scalar_type(), false, compute)));
+  check_xview_saved(inv, lse2, cpos, P->g,
+                    "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
+  return xview_backward_body(h, inv, grad_scalar(grad_out), *P, nullptr, dtau,
+                             [&](void* zq, void* coef, void* zt, const float*, hipStream_t stream) {
+                               launch_xview_coef(P->comp, zq, lse2.data_ptr<float>(), cpos.data_ptr<float>(), P->g, coef,
+                                                 zt, stream);
+                             });
+}
+
+at::Tensor xview_backward(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& lse2, const at::Tensor& cpos,
+                          const at::Tensor& grad_out, double T, const std::string& compute) {
+  return xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, nullptr);
+}
+
+// xview_backward plus the temperature gradient: (dh, dtau); dh is bitwise xview_backward's.
+std::tuple<at::Tensor, at::Tensor> xview_backward_tau(const at::Tensor& h, const at::Tensor& inv,
+                                                      const at::Tensor& lse2, const at::Tensor& cpos,
+                                                      const at::Tensor& grad_out, double T,
+                                                      const std::string& compute) {
+  at::Tensor dtau;
+  auto dh = xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, &dtau);
+  return {dh, dtau};
+}
+
+// ---- pairwise sigmoid loss, the SigLIP form (kernels/xview_kernels.hip) ----------------------------
+// Stacked views h = [h1; h2] on the current stream: the row prologue and the N x N tile GEMM with the
+// softplus epilogue. The compute dtype resolves as for xview_forward ("fp8" computes in fp16).
+// Returns {loss, inv}: nothing else needs saving (no normaliser; the backward runs the prologue again).
 std::vector<at::Tensor> xview_sigmoid_forward(const at::Tensor& h, double T, double bias, const std::string& compute) {
   check_input(h, "h");
   check_stacked(h);
@@ -433,8 +457,7 @@ std::vector<at::Tensor> xview_sigmoid_forward(const at::Tensor& h, double T, dou
 }
 
 // (dh, dtau, dbias), the last two times grad_out as 0-d fp32 tensors, undefined unless wanted; dh is
-// bitwise the same with or without them. Shaped like xview_backward_impl: buffers live only as long
-// as a stage needs them.
+// bitwise the same with or without them.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> xview_sigmoid_backward(const at::Tensor& h, const at::Tensor& inv,
                                                                       const at::Tensor& grad_out, double T, double bias,
                                                                       const std::string& compute, bool want_tau,
@@ -442,35 +465,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> xview_sigmoid_backward(const at::
   check_input(h, "h");
   check_stacked(h);
   const at::DeviceGuard guard(h.device());
-  const DType comp = backward_dtype(choose_compute(h.scalar_type(), false, compute));
-  auto P = xview_plan(h, T, comp);
+  auto P = xview_plan(h, T, backward_dtype(choose_compute(h.scalar_type(), false, compute)));
   const Geometry& g = P->g;
-  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat,
-               "xview_sigmoid_backward: inv must be float32 [rows] (xview_sigmoid_forward's output)");
-  const hipStream_t stream = cur_stream(h);
+  check_inv(inv, g);
   auto go = grad_scalar(grad_out);
-  auto coef = at::empty({(long)xview_coef_bytes(comp, g)}, opts(h, at::kByte));
-  auto zt = at::empty({(long)xview_zt_bytes(comp, g)}, opts(h, at::kByte));
-  auto bias_part = at::empty({(long)(xview_sigmoid_bias_part_bytes(g) / 4)}, opts(h, at::kFloat));
-  {
-    // the unit rows again, released once the coefficients exist (launch_prep is bitwise repeatable)
-    const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
-    const at::Tensor pos = sigmoid_pos_cos(h, inv, comp, g);
-    launch_xview_sigmoid_coef(comp, st[0].data_ptr(), g, (float)bias, coef.data_ptr(), zt.data_ptr(),
-                              bias_part.data_ptr<float>(), stream, pos.defined() ? pos.data_ptr<float>() : nullptr);
-  }
-  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
-  launch_xview_dz(comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
-  at::Tensor dot, dtau, dbias;
-  auto dh = xview_backward_tail(h, inv, go, dz, coef, zt, g, stream, &dot);
-  if (want_tau) {
-    dtau = at::empty({}, opts(h, at::kFloat));
-    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau.data_ptr<float>(), g, stream);
-  }
+  at::Tensor bias_part, dtau, dbias;
+  auto dh = xview_backward_body(h, inv, go, *P, &bias_part, want_tau ? &dtau : nullptr,
+                                [&](void* zq, void* coef, void* zt, const float* pos, hipStream_t stream) {
+                                  launch_xview_sigmoid_coef(P->comp, zq, g, (float)bias, coef, zt,
+                                                            bias_part.data_ptr<float>(), stream, pos);
+                                });
   if (want_bias) {
     dbias = at::empty({}, opts(h, at::kFloat));
     launch_xview_sigmoid_bias_grad(bias_part.data_ptr<float>(), go.data_ptr<float>(), dbias.data_ptr<float>(), g,
-                                   stream);
+                                   cur_stream(h));
   }
   return {dh, dtau, dbias};
 }
@@ -522,31 +530,48 @@ at::Tensor xview_dist_lse(const at::Tensor& part, const at::Tensor& ypos, at::Te
   return loss;
 }
 
-// Rank-local backward from the gathered rows and LSE: the slots' transposes, then per side the
-// coefficient block (one buffer, 4 n_pad W n_pad bytes) and its dZ rows, then the normalisation
-// backward with the global scale grad_out / (2N tau).
+// The rank-local backward of both losses from the gathered rows, after the caller's checks: the
+// slots' transposes, then per side the coefficient block (one buffer, 4 n_pad W n_pad bytes) and its
+// dZ rows, then the normalisation backward with the global scale grad_out / (2N tau).
+// launch_coef(side, coef, pos_cos, stream): one side's coefficient block. bias_part as in
+// xview_backward_body (allocated after coef; the pairs' cosines live across the two sides); dot as
+// xview_backward_tail's.
+template <class LaunchCoef>
+static at::Tensor xview_dist_backward_body(const at::Tensor& h, const at::Tensor& zq_all, const at::Tensor& inv,
+                                           const at::Tensor& go, const Plan& P, at::Tensor* bias_part, at::Tensor* dot,
+                                           LaunchCoef launch_coef) {
+  const Geometry& g = P.g;
+  const hipStream_t stream = cur_stream(h);
+  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(h, at::kByte));
+  auto coef = at::empty({(long)xview_coef_bytes(P.comp, g)}, opts(h, at::kByte));
+  if (bias_part) *bias_part = at::empty({(long)(xview_sigmoid_bias_part_bytes(g) / 4)}, opts(h, at::kFloat));
+  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
+  launch_xview_dist_zt(P.comp, zq_all.data_ptr(), g, g.world, zt.data_ptr(), stream);
+  {
+    const at::Tensor pos = bias_part ? sigmoid_pos_cos(h, inv, P.comp, g) : at::Tensor();
+    for (int side = 0; side < 2; ++side) {
+      launch_coef(side, coef.data_ptr(), pos.defined() ? pos.data_ptr<float>() : nullptr, stream);
+      launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, g.world, side, dz.data_ptr<float>(), false, stream);
+    }
+  }
+  coef.reset();
+  zt.reset();
+  return xview_backward_tail(h, inv, go, dz, g, stream, dot);
+}
+
 at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, const at::Tensor& inv,
                                const at::Tensor& lse2_all, const at::Tensor& cpos, const at::Tensor& grad_out,
                                const Plan& P) {
-  check_input(h, "h");
+  check_h(h, P.g);
   check_xview_dist(zq_all, P);
-  const Geometry& g = P.g;
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  check_xview_saved(inv, lse2_all, cpos, g,
+  check_xview_saved(inv, lse2_all, cpos, P.g,
                     "xview_dist_backward: inv [rows], cpos [rows_pad], lse2_all [world*rows_pad] in float32");
   const at::DeviceGuard guard(h.device());
-  const hipStream_t stream = cur_stream(h);
-  auto go = grad_scalar(grad_out);
-  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(h, at::kByte));
-  auto coef = at::empty({(long)xview_coef_bytes(P.comp, g)}, opts(h, at::kByte));
-  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
-  launch_xview_dist_zt(P.comp, zq_all.data_ptr(), g, zt.data_ptr(), stream);
-  for (int side = 0; side < 2; ++side) {
-    launch_xview_dist_coef(P.comp, zq_all.data_ptr(), lse2_all.data_ptr<float>(), cpos.data_ptr<float>(), g, side,
-                           coef.data_ptr(), stream);
-    launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), stream);
-  }
-  return xview_backward_tail(h, inv, go, dz, coef, zt, g, stream);
+  return xview_dist_backward_body(h, zq_all, inv, grad_scalar(grad_out), P, nullptr, nullptr,
+                                  [&](int side, void* coef, const float*, hipStream_t stream) {
+                                    launch_xview_dist_coef(P.comp, zq_all.data_ptr(), lse2_all.data_ptr<float>(),
+                                                           cpos.data_ptr<float>(), P.g, side, coef, stream);
+                                  });
 }
 
 // ---- distributed pairwise sigmoid loss: stage ops (parallel/sigmoid.py and parallel/emulate.py call
@@ -555,82 +580,87 @@ at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, co
 // caller's lpart (float64 [xview_sigmoid_dist_tiles]); every tile has its own place there. h, inv:
 // this rank's rows and prep's inv: a 16-bit plan whose slots include the own one takes the positives'
 // cosines from them (the own slot alone holds positives).
+static void check_lpart(const at::Tensor& lpart, const Geometry& g) {
+  check_input(lpart, "lpart");
+  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(g) && lpart.scalar_type() == at::kDouble,
+               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
+}
+
 void xview_sigmoid_dist_fwd(const at::Tensor& zq_all, const Plan& P, at::Tensor& lpart, const at::Tensor& h,
                             const at::Tensor& inv, double bias, int q_lo, int q_hi, int q_skip) {
   check_xview_dist(zq_all, P);
-  check_input(lpart, "lpart");
-  check_input(h, "h");
   const Geometry& g = P.g;
-  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(g) && lpart.scalar_type() == at::kDouble,
-               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows]");
+  check_lpart(lpart, g);
+  check_h(h, g);
+  check_inv(inv, g);
   const at::DeviceGuard guard(zq_all.device());
   const bool own = q_lo <= g.rank && g.rank < q_hi && q_skip != g.rank;
   const at::Tensor pos = own ? sigmoid_pos_cos(h, inv, P.comp, g) : at::Tensor();
-  launch_xview_sigmoid_dist_fwd(P.comp, zq_all.data_ptr(), g, (float)bias, q_lo, q_hi, q_skip, lpart.data_ptr<double>(),
-                                cur_stream(zq_all), pos.defined() ? pos.data_ptr<float>() : nullptr);
+  launch_xview_sigmoid_dist_fwd(P.comp, zq_all.data_ptr(), nullptr, g, (float)bias, q_lo, q_hi, q_skip,
+                                lpart.data_ptr<double>(), cur_stream(zq_all),
+                                pos.defined() ? pos.data_ptr<float>() : nullptr);
 }
 
 // This rank's share of the loss, a 0-d float64 tensor (a SUM over the ranks, rounded to float32 once,
 // gives the loss).
 at::Tensor xview_sigmoid_dist_loss(const at::Tensor& lpart, const Plan& P) {
-  check_input(lpart, "lpart");
-  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(P.g) && lpart.scalar_type() == at::kDouble,
-               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
+  check_lpart(lpart, P.g);
   const at::DeviceGuard guard(lpart.device());
   auto share = at::empty({}, opts(lpart, at::kDouble));
   launch_xview_sigmoid_dist_loss(lpart.data_ptr<double>(), P.g, share.data_ptr<double>(), cur_stream(lpart));
   return share;
 }
 
-// Rank-local backward from the gathered rows: the slots' transposes, then per side the coefficient
-// block (one buffer) and its dZ rows, then the normalisation backward with the global scale. Returns
-// (dh, shares): shares float64 [2] = this rank's shares of (dL/dtau, dL/dbias) times grad_out (an entry
-// not wanted is zero), undefined if neither is wanted; dh is bitwise the same either way.
-std::tuple<at::Tensor, at::Tensor> xview_sigmoid_dist_backward(const at::Tensor& h, const at::Tensor& zq_all,
-                                                               const at::Tensor& inv, const at::Tensor& grad_out,
-                                                               const Plan& P, double bias, bool want_tau,
-                                                               bool want_bias) {
-  check_input(h, "h");
-  check_xview_dist(zq_all, P);
-  const Geometry& g = P.g;
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat,
-               "xview_sigmoid_dist_backward: inv must be float32 [rows]");
-  const at::DeviceGuard guard(h.device());
-  const hipStream_t stream = cur_stream(h);
-  auto go = grad_scalar(grad_out);
-  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(h, at::kByte));
-  auto coef = at::empty({(long)xview_coef_bytes(P.comp, g)}, opts(h, at::kByte));
-  auto bias_part = at::empty({(long)(xview_sigmoid_bias_part_bytes(g) / 4)}, opts(h, at::kFloat));
-  auto dz = at::empty({(long)(xview_dz_bytes(g) / 4)}, opts(h, at::kFloat));
-  launch_xview_dist_zt(P.comp, zq_all.data_ptr(), g, zt.data_ptr(), stream);
-  {
-    const at::Tensor pos = sigmoid_pos_cos(h, inv, P.comp, g);
-    for (int side = 0; side < 2; ++side) {
-      launch_xview_sigmoid_dist_coef(P.comp, zq_all.data_ptr(), g, (float)bias, side, coef.data_ptr(),
-                                     side == 0 ? bias_part.data_ptr<float>() : nullptr, stream,
-                                     pos.defined() ? pos.data_ptr<float>() : nullptr);
-      launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), stream);
-    }
-  }
-  at::Tensor dot, shares;
-  auto dh = xview_backward_tail(h, inv, go, dz, coef, zt, g, stream, &dot);
+// This rank's fp64 shares of (dL/dtau, dL/dbias) times grad_out, float64 [2] (an entry not wanted is
+// zero); undefined if neither is wanted. dot: xview_backward_tail's; bias_part: side 0's sums of C.
+static at::Tensor sigmoid_scalar_shares(const at::Tensor& dot, const at::Tensor& bias_part, const at::Tensor& go,
+                                        const Geometry& g, bool want_tau, bool want_bias, hipStream_t stream) {
+  at::Tensor shares;
   if (want_tau || want_bias) {
-    shares = at::zeros({2}, opts(h, at::kDouble));
+    shares = at::zeros({2}, opts(dot, at::kDouble));
     if (want_tau)
       launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream, shares.data_ptr<double>());
     if (want_bias)
       launch_xview_sigmoid_bias_grad(bias_part.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream,
                                      shares.data_ptr<double>() + 1);
   }
-  return {dh, shares};
+  return shares;
+}
+
+// Rank-local backward from the gathered rows (xview_dist_backward_body). Returns (dh, shares):
+// sigmoid_scalar_shares'; dh is bitwise the same with or without them.
+std::tuple<at::Tensor, at::Tensor> xview_sigmoid_dist_backward(const at::Tensor& h, const at::Tensor& zq_all,
+                                                               const at::Tensor& inv, const at::Tensor& grad_out,
+                                                               const Plan& P, double bias, bool want_tau,
+                                                               bool want_bias) {
+  check_h(h, P.g);
+  check_xview_dist(zq_all, P);
+  check_inv(inv, P.g);
+  const at::DeviceGuard guard(h.device());
+  auto go = grad_scalar(grad_out);
+  at::Tensor bias_part, dot;
+  auto dh = xview_dist_backward_body(
+      h, zq_all, inv, go, P, &bias_part, &dot, [&](int side, void* coef, const float* pos, hipStream_t stream) {
+        launch_xview_sigmoid_dist_coef(P.comp, zq_all.data_ptr(), nullptr, 0, P.g, (float)bias, side, coef,
+                                       side == 0 ? bias_part.data_ptr<float>() : nullptr, stream, pos);
+      });
+  return {dh, sigmoid_scalar_shares(dot, bias_part, go, P.g, want_tau, want_bias, cur_stream(h))};
 }
 
 // ---- the same loss, one rank slot at a time (exchange="ring"): stage ops shared by
 // parallel/sigmoid.py's RingSigmoidFunction and parallel/emulate.py -----------------------------------
 // zq [rows_pad, ld_k]: this rank's own prep rows; rows_q: the same shape, rank q's rows (q == rank: zq).
+// bias_part and the fp32 slab dz are the caller's from the first block to xview_sigmoid_ring_finish.
+static void check_bias_part(const at::Tensor& bias_part, const Geometry& g) {
+  check_input(bias_part, "bias_part");
+  NTXENT_CHECK(bias_part.numel() * 4 == (long)xview_sigmoid_bias_part_bytes(g) && bias_part.scalar_type() == at::kFloat,
+               "bias_part must be float32 [n_pad / 128 * world * n_pad / 128 * 4]");
+}
+static void check_dz_slab(const at::Tensor& dz, const Geometry& g) {
+  check_input(dz, "dz");
+  NTXENT_CHECK(dz.numel() * 4 == (long)xview_dz_bytes(g) && dz.scalar_type() == at::kFloat,
+               "dz must be float32 [rows_pad * dim_n]");
+}
 static void check_xview_block(const at::Tensor& zq, const at::Tensor& rows_q, int q, const Plan& P) {
   check_input(zq, "zq");
   check_input(rows_q, "rows_q");
@@ -645,12 +675,10 @@ static void check_xview_block(const at::Tensor& zq, const at::Tensor& rows_q, in
 // 16-bit plans: the pairs' cosines of this rank's rows (sigmoid_pos_cos), the own block's diagonal in
 // the block backward; undefined (None) for fp32 plans.
 c10::optional<at::Tensor> xview_sigmoid_pos_cos(const at::Tensor& h, const at::Tensor& inv, const Plan& P) {
-  check_input(h, "h");
-  const Geometry& g = P.g;
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows]");
+  check_h(h, P.g);
+  check_inv(inv, P.g);
   const at::DeviceGuard guard(h.device());
-  const at::Tensor pos = sigmoid_pos_cos(h, inv, P.comp, g);
+  const at::Tensor pos = sigmoid_pos_cos(h, inv, P.comp, P.g);
   if (!pos.defined()) return c10::nullopt;
   return pos;
 }
@@ -661,17 +689,14 @@ c10::optional<at::Tensor> xview_sigmoid_pos_cos(const at::Tensor& h, const at::T
 void xview_sigmoid_block_fwd(const at::Tensor& zq, const at::Tensor& rows_q, int q, const Plan& P, at::Tensor& lpart,
                              const at::Tensor& h, const at::Tensor& inv, double bias) {
   check_xview_block(zq, rows_q, q, P);
-  check_input(lpart, "lpart");
-  check_input(h, "h");
   const Geometry& g = P.g;
-  NTXENT_CHECK(lpart.numel() * 8 == (long)xview_sigmoid_scratch_bytes(g) && lpart.scalar_type() == at::kDouble,
-               "lpart must be float64 [n_pad / 128 * world * n_pad / 128]");
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat, "inv must be float32 [rows]");
+  check_lpart(lpart, g);
+  check_h(h, g);
+  check_inv(inv, g);
   const at::DeviceGuard guard(zq.device());
   const at::Tensor pos = q == g.rank ? sigmoid_pos_cos(h, inv, P.comp, g) : at::Tensor();
-  launch_xview_sigmoid_block_fwd(P.comp, zq.data_ptr(), rows_q.data_ptr(), g, (float)bias, q, lpart.data_ptr<double>(),
-                                 cur_stream(zq), pos.defined() ? pos.data_ptr<float>() : nullptr);
+  launch_xview_sigmoid_dist_fwd(P.comp, zq.data_ptr(), rows_q.data_ptr(), g, (float)bias, q, q + 1, -1,
+                                lpart.data_ptr<double>(), cur_stream(zq), pos.defined() ? pos.data_ptr<float>() : nullptr);
 }
 
 // One block of the backward: rows_q transposed into zt, then for side 0 and side 1 the coefficient
@@ -685,17 +710,13 @@ void xview_sigmoid_block_backward(const at::Tensor& zq, const at::Tensor& rows_q
   check_xview_block(zq, rows_q, q, P);
   check_input(coef, "coef");
   check_input(zt, "zt");
-  check_input(bias_part, "bias_part");
-  check_input(dz, "dz");
   const Geometry& g = P.g;
   NTXENT_CHECK(coef.numel() * coef.element_size() == (long)xview_block_coef_bytes(P.comp, g),
                "coef must hold xview_block_coef_bytes");
   NTXENT_CHECK(zt.numel() * zt.element_size() == (long)xview_block_zt_bytes(P.comp, g),
                "zt must hold xview_block_zt_bytes");
-  NTXENT_CHECK(bias_part.numel() * 4 == (long)xview_sigmoid_bias_part_bytes(g) && bias_part.scalar_type() == at::kFloat,
-               "bias_part must be float32 [n_pad / 128 * world * n_pad / 128 * 4]");
-  NTXENT_CHECK(dz.numel() * 4 == (long)xview_dz_bytes(g) && dz.scalar_type() == at::kFloat,
-               "dz must be float32 [rows_pad * dim_n]");
+  check_bias_part(bias_part, g);
+  check_dz_slab(dz, g);
   const float* pos = nullptr;
   if (pos_cos.has_value() && pos_cos->defined()) {
     check_input(*pos_cos, "pos_cos");
@@ -705,45 +726,31 @@ void xview_sigmoid_block_backward(const at::Tensor& zq, const at::Tensor& rows_q
   NTXENT_CHECK((pos != nullptr) == (P.comp != DType::F32), "pos_cos with 16-bit plans and only there");
   const at::DeviceGuard guard(zq.device());
   const hipStream_t stream = cur_stream(zq);
-  launch_xview_block_zt(P.comp, rows_q.data_ptr(), g, zt.data_ptr(), stream);
+  launch_xview_dist_zt(P.comp, rows_q.data_ptr(), g, 1, zt.data_ptr(), stream);
   for (int side = 0; side < 2; ++side) {
-    launch_xview_sigmoid_block_coef(P.comp, zq.data_ptr(), rows_q.data_ptr(), g, (float)bias, q, side, coef.data_ptr(),
-                                    side == 0 ? bias_part.data_ptr<float>() : nullptr, stream, pos);
-    launch_xview_block_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, side, dz.data_ptr<float>(), !first, stream);
+    launch_xview_sigmoid_dist_coef(P.comp, zq.data_ptr(), rows_q.data_ptr(), q, g, (float)bias, side, coef.data_ptr(),
+                                   side == 0 ? bias_part.data_ptr<float>() : nullptr, stream, pos);
+    launch_xview_dist_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, 1, side, dz.data_ptr<float>(), !first, stream);
   }
 }
 
-// After all W blocks: the normalisation backward of the slab with the global scale, and the fp64 shares
-// as xview_sigmoid_dist_backward forms them. Returns (dh, shares); shares undefined if neither is wanted.
+// After all W blocks (the caller has released coef and zt): the normalisation backward of the slab with
+// the global scale. Returns (dh, shares): sigmoid_scalar_shares', as xview_sigmoid_dist_backward.
 std::tuple<at::Tensor, at::Tensor> xview_sigmoid_ring_finish(const at::Tensor& h, const at::Tensor& inv,
                                                              const at::Tensor& grad_out, const at::Tensor& dz,
                                                              const at::Tensor& bias_part, const Plan& P, bool want_tau,
                                                              bool want_bias) {
-  check_input(h, "h");
-  check_input(dz, "dz");
-  check_input(bias_part, "bias_part");
   const Geometry& g = P.g;
-  NTXENT_CHECK(h.dim() == 2 && h.size(0) == g.rows && h.size(1) == g.dim, "h shape does not match plan");
-  NTXENT_CHECK(inv.numel() == g.rows && inv.scalar_type() == at::kFloat,
-               "xview_sigmoid_ring_finish: inv must be float32 [rows]");
-  NTXENT_CHECK(dz.numel() * 4 == (long)xview_dz_bytes(g) && dz.scalar_type() == at::kFloat,
-               "dz must be float32 [rows_pad * dim_n]");
-  NTXENT_CHECK(bias_part.numel() * 4 == (long)xview_sigmoid_bias_part_bytes(g) && bias_part.scalar_type() == at::kFloat,
-               "bias_part must be float32 [n_pad / 128 * world * n_pad / 128 * 4]");
+  check_h(h, g);
+  check_inv(inv, g);
+  check_dz_slab(dz, g);
+  check_bias_part(bias_part, g);
   const at::DeviceGuard guard(h.device());
   const hipStream_t stream = cur_stream(h);
   auto go = grad_scalar(grad_out);
-  at::Tensor none_a, none_b, dot, shares;  // the caller owns coef and zt
-  auto dh = xview_backward_tail(h, inv, go, dz, none_a, none_b, g, stream, &dot);
-  if (want_tau || want_bias) {
-    shares = at::zeros({2}, opts(h, at::kDouble));
-    if (want_tau)
-      launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream, shares.data_ptr<double>());
-    if (want_bias)
-      launch_xview_sigmoid_bias_grad(bias_part.data_ptr<float>(), go.data_ptr<float>(), nullptr, g, stream,
-                                     shares.data_ptr<double>() + 1);
-  }
-  return {dh, shares};
+  at::Tensor dot;
+  auto dh = xview_backward_tail(h, inv, go, dz, g, stream, &dot);
+  return {dh, sigmoid_scalar_shares(dot, bias_part, go, g, want_tau, want_bias, stream)};
 }
 
 at::Tensor transpose(const at::Tensor& zq, const Plan& P, const c10::optional<at::Tensor>& zqt_out) {

@@ -35,16 +35,18 @@ def _one_element(v, name: str):
     return v
 
 
-def _host_values(temperature, bias):
-    """(tau, bias) as host floats. One-element tensors are read on the host: two tensors on the same
-    GPU together, in a single copy (one host sync per forward); tensors on two different GPUs cost a
-    sync each, CPU tensors none."""
+def _scalar_args(temperature, bias):
+    """What the sigmoid Functions take of ``(temperature, bias)``: ``(tv, bv, tau, bias_t)``, the two as
+    host floats and, where autograd tracks it, the tensor whose gradient is wanted (None otherwise).
+    One-element tensors are read on the host: two tensors on the same GPU together, in a single copy
+    (one host sync per forward); tensors on two different GPUs cost a sync each, CPU tensors none."""
     vals = [_one_element(temperature, "temperature"), _one_element(bias, "bias")]
     dev = [i for i, v in enumerate(vals) if isinstance(v, torch.Tensor) and v.is_cuda]
     if len(dev) == 2 and vals[0].device == vals[1].device:
-        both = torch.stack([vals[0].detach().reshape(()).double(), vals[1].detach().reshape(()).double()]).tolist()
-        return float(both[0]), float(both[1])
-    return tuple(float(v.detach().item()) if isinstance(v, torch.Tensor) else float(v) for v in vals)
+        host = torch.stack([vals[0].detach().reshape(()).double(), vals[1].detach().reshape(()).double()]).tolist()
+    else:
+        host = [float(v.detach().item()) if isinstance(v, torch.Tensor) else float(v) for v in vals]
+    return (float(host[0]), float(host[1]), *(v if temperature_wants_grad(v) else None for v in vals))
 
 
 class SigmoidFunction(torch.autograd.Function):
@@ -108,9 +110,7 @@ def sigmoid_loss(h: torch.Tensor, temperature=0.1, bias=-10.0, *, z2: Optional[t
     comp = resolve_compute(h.dtype, use_mixed_precision, compute)
     if comp == "fp8":
         comp = "fp16"
-    tv, bv = _host_values(temperature, bias)
-    tau = temperature if temperature_wants_grad(temperature) else None
-    bias_t = bias if temperature_wants_grad(bias) else None
+    tv, bv, tau, bias_t = _scalar_args(temperature, bias)
     return SigmoidFunction.apply(h, tv, bv, comp, tau, bias_t)
 
 

@@ -109,11 +109,10 @@ def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperatur
     prep writes a buffer of its own, and a rank's ``visit`` hands it the other virtual ranks' ``zq`` in
     ring order, q = r, r-1, ..., r-W+1, without copying."""
     from .infonce import _CDT, xview_compute
-    from .sigmoid import (EXCHANGES, sigmoid_ring_stage_backward, sigmoid_ring_stage_forward,
+    from .sigmoid import (_check_exchange, sigmoid_ring_stage_backward, sigmoid_ring_stage_forward,
                           sigmoid_stage_forward)
 
-    if exchange not in EXCHANGES:
-        raise ValueError(f"emulated_sigmoid_forward_backward: exchange must be one of {EXCHANGES}, got {exchange!r}")
+    _check_exchange(exchange, "emulated_sigmoid_forward_backward")
     C = _ext.load()
     W = len(shards)
     R, d = shards[0].shape
@@ -122,6 +121,8 @@ def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperatur
     plans = [C.get_plan(R, d, W, r, float(temperature), comp, dev.index) for r in range(W)]
     Rpad = plans[0].rows_pad
     hs = [x.contiguous() for x in shards]
+    go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
+    bias, wants = float(bias), (bool(want_tau), bool(want_bias))
     if exchange == "ring":
         preps = [C.prep(hs[r], plans[r]) for r in range(W)]
         zqs = [p[0] for p in preps]
@@ -132,29 +133,27 @@ def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperatur
                     fn((r - s) % W, zqs[(r - s) % W], 0)
             return visit
 
-        loss = torch.zeros((), dtype=torch.float64, device=dev)
-        for r in range(W):
-            loss = loss + sigmoid_ring_stage_forward(C, plans[r], zqs[r], hs[r], preps[r][1], float(bias), visit_of(r))
-        go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
-        grads, scalars = [], torch.zeros((2,), dtype=torch.float64, device=dev)
-        for r in range(W):
-            dh, shares = sigmoid_ring_stage_backward(C, plans[r], zqs[r], hs[r], preps[r][1], float(bias), go,
-                                                     bool(want_tau), bool(want_bias), visit_of(r))
-            grads.append(dh)
-            if shares is not None:
-                scalars = scalars + shares  # "all-reduce" (fp64 shares)
-        scalars = scalars.float()
-        return loss.float(), grads, scalars[0] if want_tau else None, scalars[1] if want_bias else None
-    zq_all = torch.empty((W * Rpad, plans[0].ld_k), dtype=_CDT[comp], device=dev)
-    preps = [C.prep(hs[r], plans[r], zq_all[r * Rpad:(r + 1) * Rpad], None) for r in range(W)]  # "all-gather"
+        def forward(r):
+            return sigmoid_ring_stage_forward(C, plans[r], zqs[r], hs[r], preps[r][1], bias, visit_of(r))
+
+        def backward(r):
+            return sigmoid_ring_stage_backward(C, plans[r], zqs[r], hs[r], preps[r][1], bias, go, *wants, visit_of(r))
+    else:
+        zq_all = torch.empty((W * Rpad, plans[0].ld_k), dtype=_CDT[comp], device=dev)
+        preps = [C.prep(hs[r], plans[r], zq_all[r * Rpad:(r + 1) * Rpad], None) for r in range(W)]  # "all-gather"
+
+        def forward(r):
+            return sigmoid_stage_forward(C, plans[r], zq_all, hs[r], preps[r][1], bias)
+
+        def backward(r):
+            return C.xview_sigmoid_dist_backward(hs[r], zq_all, preps[r][1], go, plans[r], bias, *wants)
+
     loss = torch.zeros((), dtype=torch.float64, device=dev)
     for r in range(W):
-        loss = loss + sigmoid_stage_forward(C, plans[r], zq_all, hs[r], preps[r][1], float(bias))  # "all-reduce"
-    go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
+        loss = loss + forward(r)  # "all-reduce" (fp64 shares)
     grads, scalars = [], torch.zeros((2,), dtype=torch.float64, device=dev)
     for r in range(W):
-        dh, shares = C.xview_sigmoid_dist_backward(hs[r], zq_all, preps[r][1], go, plans[r], float(bias),
-                                                   bool(want_tau), bool(want_bias))
+        dh, shares = backward(r)
         grads.append(dh)
         if shares is not None:
             scalars = scalars + shares  # "all-reduce" (fp64 shares)

@@ -53,30 +53,40 @@ def xview_stage_forward(C, plan, zq_all: torch.Tensor, ypos: torch.Tensor, lse2_
     return C.xview_dist_lse(part, ypos, lse2_all, cpos, plan), cpos
 
 
+def _gather_prologue(C, h: torch.Tensor, temperature: float, compute: str, group, overlap: bool):
+    """What the gather Functions' forwards open with: this rank's plan, ``prep`` of the contiguous ``h``
+    straight into its slot of ``zq_all [W Rpad][ld_k]`` and the all-gather of the slots, started there:
+    the gather runs in place. Returns ``(plan, zq_all, prep's outputs, wait)``. ``wait`` is for the
+    stage forward: it makes the stream wait for the rows of the other ranks, or is None if they need
+    no waiting for (without ``overlap`` that is done here)."""
+    W, r = _world(group)
+    R, d = h.shape
+    plan = C.get_plan(R, d, W, r, float(temperature), compute, h.device.index)
+    Rpad = plan.rows_pad
+    zq_all = torch.empty((W * Rpad, plan.ld_k), dtype=_CDT[compute], device=h.device)
+    zq = zq_all[r * Rpad:(r + 1) * Rpad]
+    st = C.prep(h, plan, zq, None)
+    work = _all_gather_into(zq_all, zq, group, async_op=True) if W > 1 else None
+
+    def wait():
+        if work is not None:
+            with span("fwd_rows"):
+                work.wait()
+
+    if not overlap:
+        wait()
+    return plan, zq_all, st, wait if overlap else None
+
+
 class DistInfoNCEFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h: torch.Tensor, temperature: float, compute: str, group, overlap: bool):
         C = _ext.load()
-        W, r = _world(group)
         h = h.contiguous()
-        R, d = h.shape
-        plan = C.get_plan(R, d, W, r, float(temperature), compute, h.device.index)
-        Rpad = plan.rows_pad
-        # prep writes straight into this rank's slot: the gather runs in place
-        zq_all = torch.empty((W * Rpad, plan.ld_k), dtype=_CDT[compute], device=h.device)
-        zq = zq_all[r * Rpad:(r + 1) * Rpad]
-        _, inv, ypos, _ = C.prep(h, plan, zq, None)
-        work = _all_gather_into(zq_all, zq, group, async_op=True) if W > 1 else None
-
-        def wait():
-            if work is not None:
-                with span("fwd_rows"):
-                    work.wait()
-
-        if not overlap:
-            wait()
+        plan, zq_all, (_, inv, ypos, _), wait = _gather_prologue(C, h, temperature, compute, group, overlap)
+        W, r, Rpad = plan.world, plan.rank, plan.rows_pad
         lse2_all = torch.empty((W * Rpad,), dtype=torch.float32, device=h.device)
-        share, cpos = xview_stage_forward(C, plan, zq_all, ypos, lse2_all, wait if overlap else None)
+        share, cpos = xview_stage_forward(C, plan, zq_all, ypos, lse2_all, wait)
         if W > 1:
             mine = lse2_all[r * Rpad:(r + 1) * Rpad].clone()
             with span("lse_loss"):

@@ -41,18 +41,42 @@ elements, twice the gather's, and the same 8 B and 16 B.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
 import torch.distributed as dist
 
 from ..ops import _ext, reference
-from ..ops.ntxent import _stack_views, _tau_grad, _tau_like, _TemperatureModule, temperature_wants_grad
-from ..ops.sigmoid import _host_values, sigmoid_loss
+from ..ops.ntxent import _stack_views, _tau_grad, _tau_like, _TemperatureModule
+from ..ops.sigmoid import _scalar_args, sigmoid_loss
 from .commstats import span
-from .distributed import _all_gather_into, _world
-from .infonce import _CDT, _gather, xview_compute
+from .distributed import _world
+from .infonce import _gather, _gather_prologue, xview_compute
 from .ring import _ring
+
+EXCHANGES = ("gather", "ring")
+
+
+def _check_exchange(exchange: str, who: str) -> None:
+    if exchange not in EXCHANGES:
+        raise ValueError(f"{who}: exchange must be one of {EXCHANGES}, got {exchange!r}")
+
+
+def _scalar_grads(shares: Optional[torch.Tensor], tau_like, bias_like, world: int, group):
+    """``(dtau, dbias)`` of the global loss from this rank's fp64 shares ``[2]``: their sum over the
+    ranks (16 B), on the GPU paths rounded to fp32 once each, as ``_tau_like`` kept the two tensors. A
+    like of None: that gradient is not wanted, and None is returned for it; with neither nothing is
+    communicated."""
+    if tau_like is None and bias_like is None:
+        return None, None
+    if world > 1:
+        with span("sigmoid_scalars") if shares.is_cuda else contextlib.nullcontext():
+            dist.all_reduce(shares, op=dist.ReduceOp.SUM, group=group)
+    if shares.is_cuda:
+        shares = shares.float()
+    return (None if tau_like is None else _tau_grad(shares[0], tau_like),
+            None if bias_like is None else _tau_grad(shares[1], bias_like))
 
 
 def sigmoid_stage_forward(C, plan, zq_all: torch.Tensor, h: torch.Tensor, inv: torch.Tensor, bias: float, wait=None):
@@ -77,26 +101,10 @@ class DistSigmoidFunction(torch.autograd.Function):
     def forward(ctx, h: torch.Tensor, temperature: float, bias: float, compute: str, group, overlap: bool,
                 tau: Optional[torch.Tensor] = None, bias_t: Optional[torch.Tensor] = None):
         C = _ext.load()
-        W, r = _world(group)
         h = h.contiguous()
-        R, d = h.shape
-        plan = C.get_plan(R, d, W, r, float(temperature), compute, h.device.index)
-        Rpad = plan.rows_pad
-        # prep writes straight into this rank's slot: the gather runs in place
-        zq_all = torch.empty((W * Rpad, plan.ld_k), dtype=_CDT[compute], device=h.device)
-        zq = zq_all[r * Rpad:(r + 1) * Rpad]
-        _, inv, _, _ = C.prep(h, plan, zq, None)
-        work = _all_gather_into(zq_all, zq, group, async_op=True) if W > 1 else None
-
-        def wait():
-            if work is not None:
-                with span("fwd_rows"):
-                    work.wait()
-
-        if not overlap:
-            wait()
-        share = sigmoid_stage_forward(C, plan, zq_all, h, inv, float(bias), wait if overlap else None)
-        if W > 1:
+        plan, zq_all, (_, inv, _, _), wait = _gather_prologue(C, h, temperature, compute, group, overlap)
+        share = sigmoid_stage_forward(C, plan, zq_all, h, inv, float(bias), wait)
+        if plan.world > 1:
             with span("sigmoid_loss"):
                 dist.all_reduce(share, op=dist.ReduceOp.SUM, group=group)  # fp64 shares (8 B)
         ctx.plan, ctx.bias, ctx.group = plan, float(bias), group
@@ -108,19 +116,11 @@ class DistSigmoidFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         h, zq_all, inv = ctx.saved_tensors
-        want_tau = ctx.tau is not None and ctx.needs_input_grad[6]
-        want_bias = ctx.bias_like is not None and ctx.needs_input_grad[7]
+        tau = ctx.tau if ctx.needs_input_grad[6] else None
+        bias_like = ctx.bias_like if ctx.needs_input_grad[7] else None
         dh, shares = _ext.load().xview_sigmoid_dist_backward(h, zq_all, inv, grad_out.reshape(1), ctx.plan, ctx.bias,
-                                                             want_tau, want_bias)
-        dtau = dbias = None
-        if want_tau or want_bias:
-            if ctx.plan.world > 1:
-                with span("sigmoid_scalars"):
-                    dist.all_reduce(shares, op=dist.ReduceOp.SUM, group=ctx.group)  # fp64 shares (16 B)
-            both = shares.float()  # one rounding to fp32 each
-            dtau = _tau_grad(both[0], ctx.tau) if want_tau else None
-            dbias = _tau_grad(both[1], ctx.bias_like) if want_bias else None
-        return dh, None, None, None, None, None, dtau, dbias
+                                                             tau is not None, bias_like is not None)
+        return dh, None, None, None, None, None, *_scalar_grads(shares, tau, bias_like, ctx.plan.world, ctx.group)
 
 
 # ---------------------------------------------------------------------------------------
@@ -191,22 +191,12 @@ class RingSigmoidFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         h, zq, inv = ctx.saved_tensors
-        want_tau = ctx.tau is not None and ctx.needs_input_grad[5]
-        want_bias = ctx.bias_like is not None and ctx.needs_input_grad[6]
+        tau = ctx.tau if ctx.needs_input_grad[5] else None
+        bias_like = ctx.bias_like if ctx.needs_input_grad[6] else None
         dh, shares = sigmoid_ring_stage_backward(_ext.load(), ctx.plan, zq, h, inv, ctx.bias, grad_out.reshape(1),
-                                                 want_tau, want_bias, lambda fn: _ring(zq, ctx.group, fn))
-        dtau = dbias = None
-        if want_tau or want_bias:
-            if ctx.plan.world > 1:
-                with span("sigmoid_scalars"):
-                    dist.all_reduce(shares, op=dist.ReduceOp.SUM, group=ctx.group)  # fp64 shares (16 B)
-            both = shares.float()
-            dtau = _tau_grad(both[0], ctx.tau) if want_tau else None
-            dbias = _tau_grad(both[1], ctx.bias_like) if want_bias else None
-        return dh, None, None, None, None, dtau, dbias
-
-
-EXCHANGES = ("gather", "ring")
+                                                 tau is not None, bias_like is not None,
+                                                 lambda fn: _ring(zq, ctx.group, fn))
+        return dh, None, None, None, None, *_scalar_grads(shares, tau, bias_like, ctx.plan.world, ctx.group)
 
 
 def dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, *, z2: Optional[torch.Tensor] = None,
@@ -231,8 +221,7 @@ def dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, *, z2:
     Without a process group, or in a group of one, this is ``sigmoid_loss``. CPU tensors take
     ``cpu_dist_sigmoid_loss``.
     """
-    if exchange not in EXCHANGES:
-        raise ValueError(f"dist_sigmoid_loss: exchange must be one of {EXCHANGES}, got {exchange!r}")
+    _check_exchange(exchange, "dist_sigmoid_loss")
     W, _ = _world(group)
     if W == 1:
         return sigmoid_loss(h_local, temperature, bias, z2=z2, compute=compute, use_mixed_precision=use_mixed_precision)
@@ -240,9 +229,7 @@ def dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, *, z2:
     if not h.is_cuda:
         return cpu_dist_sigmoid_loss(h, temperature, bias, group=group, exchange=exchange)
     comp = xview_compute(h.dtype, use_mixed_precision, compute)
-    tv, bv = _host_values(temperature, bias)
-    tau = temperature if temperature_wants_grad(temperature) else None
-    bias_t = bias if temperature_wants_grad(bias) else None
+    tv, bv, tau, bias_t = _scalar_args(temperature, bias)
     if exchange == "ring":
         return RingSigmoidFunction.apply(h, tv, bv, comp, group, tau, bias_t)
     return DistSigmoidFunction.apply(h, tv, bv, comp, group, bool(overlap), tau, bias_t)
@@ -261,8 +248,7 @@ class DistSigmoidLoss(_TemperatureModule):
                  use_mixed_precision: bool = False, overlap: bool = True, learnable_temperature: bool = False,
                  temperature_bounds=(0.01, 1.0), learnable_bias: bool = False, exchange: str = "gather"):
         super().__init__()
-        if exchange not in EXCHANGES:
-            raise ValueError(f"DistSigmoidLoss: exchange must be one of {EXCHANGES}, got {exchange!r}")
+        _check_exchange(exchange, "DistSigmoidLoss")
         self.exchange = exchange
         self.compute = compute
         self.group = group
@@ -291,6 +277,20 @@ class DistSigmoidLoss(_TemperatureModule):
 # CPU / gloo path: the same algorithm (gather unit rows, side 0's n x N block forward, rank-local
 # backward from both sides, one all-reduce of the two scalar shares) written with torch ops.
 # ---------------------------------------------------------------------------------------
+def _cpu_backward_end(ctx, z, inv, dz, g, sum_g_cos, sum_g):
+    """What the two CPU backwards end with: the scale g / (N tau), the normalisation backward, and
+    from side 0's sums of ``G cos`` and of ``G`` (each pair counts once) this rank's shares of the scalar
+    gradients."""
+    temperature, _, W, _, group, tau_like, bias_like = ctx.meta
+    N = W * (z.shape[0] // 2)
+    dz = dz * (g / (N * temperature))
+    dot = (z * dz).sum(1, keepdim=True)
+    dh = inv.unsqueeze(1) * (dz - z * dot)
+    shares = torch.stack([-sum_g_cos / (N * temperature * temperature), sum_g / N]).double() * g.double()
+    return (dh, None, None, None, *_scalar_grads(shares, tau_like if ctx.needs_input_grad[4] else None,
+                                                 bias_like if ctx.needs_input_grad[5] else None, W, group))
+
+
 class _CpuDistSigmoidFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, temperature, bias, group, tau, bias_t):
@@ -313,9 +313,8 @@ class _CpuDistSigmoidFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         z, inv, t0, t1 = ctx.saved_tensors
-        temperature, bias, W, r, group, tau_like, bias_like = ctx.meta
+        temperature, bias, _, r, _, _, _ = ctx.meta
         n = z.shape[0] // 2
-        N = W * n
         ar = torch.arange(n)
         towers = (t0, t1)
         dz, G0 = [], None
@@ -327,19 +326,7 @@ class _CpuDistSigmoidFn(torch.autograd.Function):
             dz.append(G @ towers[1 - v])
             if v == 0:
                 G0, cos0 = G, cos
-        dz = torch.cat(dz, 0) * (g / (N * temperature))
-        dot = (z * dz).sum(1, keepdim=True)
-        dh = inv.unsqueeze(1) * (dz - z * dot)
-        want_tau = tau_like is not None and ctx.needs_input_grad[4]
-        want_bias = bias_like is not None and ctx.needs_input_grad[5]
-        dtau = dbias = None
-        if want_tau or want_bias:  # each pair counts once: side 0's block
-            shares = torch.stack([-(G0 * cos0).sum() / (N * temperature * temperature), G0.sum() / N]).double() * g.double()
-            if W > 1:
-                dist.all_reduce(shares, group=group)
-            dtau = _tau_grad(shares[0], tau_like) if want_tau else None
-            dbias = _tau_grad(shares[1], bias_like) if want_bias else None
-        return dh, None, None, None, dtau, dbias
+        return _cpu_backward_end(ctx, z, inv, torch.cat(dz, 0), g, (G0 * cos0).sum(), G0.sum())
 
 
 class _CpuRingSigmoidFn(torch.autograd.Function):
@@ -373,9 +360,8 @@ class _CpuRingSigmoidFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         z, inv = ctx.saved_tensors
-        temperature, bias, W, r, group, tau_like, bias_like = ctx.meta
+        temperature, bias, _, r, group, _, _ = ctx.meta
         n = z.shape[0] // 2
-        N = W * n
         ar = torch.arange(n)
         dz = torch.zeros_like(z)
         sums = torch.zeros(2, dtype=z.dtype)  # side 0's sum of G cos and of G: each pair counts once
@@ -394,30 +380,14 @@ class _CpuRingSigmoidFn(torch.autograd.Function):
                     sums[1] += G.sum()
 
         _ring(z, group, block)
-        dz = dz * (g / (N * temperature))
-        dot = (z * dz).sum(1, keepdim=True)
-        dh = inv.unsqueeze(1) * (dz - z * dot)
-        want_tau = tau_like is not None and ctx.needs_input_grad[4]
-        want_bias = bias_like is not None and ctx.needs_input_grad[5]
-        dtau = dbias = None
-        if want_tau or want_bias:
-            shares = torch.stack([-sums[0] / (N * temperature * temperature), sums[1] / N]).double() * g.double()
-            if W > 1:
-                dist.all_reduce(shares, group=group)
-            dtau = _tau_grad(shares[0], tau_like) if want_tau else None
-            dbias = _tau_grad(shares[1], bias_like) if want_bias else None
-        return dh, None, None, None, dtau, dbias
+        return _cpu_backward_end(ctx, z, inv, dz, g, sums[0], sums[1])
 
 
 def cpu_dist_sigmoid_loss(h_local: torch.Tensor, temperature=0.1, bias=-10.0, group=None,
                           exchange: str = "gather") -> torch.Tensor:
     """The distributed algorithm in torch ops over gloo, for CPU tensors (any float dtype);
     ``exchange`` as ``dist_sigmoid_loss``'s."""
-    if exchange not in EXCHANGES:
-        raise ValueError(f"cpu_dist_sigmoid_loss: exchange must be one of {EXCHANGES}, got {exchange!r}")
-    h = _stack_views(h_local, None)
-    tv, bv = _host_values(temperature, bias)
-    tau = temperature if temperature_wants_grad(temperature) else None
-    bias_t = bias if temperature_wants_grad(bias) else None
+    _check_exchange(exchange, "cpu_dist_sigmoid_loss")
     fn = _CpuRingSigmoidFn if exchange == "ring" else _CpuDistSigmoidFn
-    return fn.apply(h, tv, bv, group, tau, bias_t)
+    tv, bv, tau, bias_t = _scalar_args(temperature, bias)
+    return fn.apply(_stack_views(h_local, None), tv, bv, group, tau, bias_t)

@@ -12,10 +12,13 @@ with a CPU torch.Generator, in a fixed order:
   sigmoid    loss, dh, dL/dtau, dL/dbias of ``sigmoid_loss`` (tau = 0.1, bias = -10 as tensors that require grad)
   sigmoid_dist loss, dL/dtau, dL/dbias and every rank's dh of ``emulated_sigmoid_forward_backward``
              (a build without the distributed sigmoid loss prints none of these lines)
+  sigmoid_ring the same of ``emulated_sigmoid_forward_backward(..., exchange="ring")``
+             (a build without the ring exchange prints none of these lines)
 """
 from __future__ import annotations
 
 import hashlib
+import inspect
 import sys
 from pathlib import Path
 
@@ -78,11 +81,16 @@ def main():
         from ntxent_amd.parallel.emulate import emulated_sigmoid_forward_backward
     except ImportError:
         emulated_sigmoid_forward_backward = None
-    for W, n, d, comp in DIST if emulated_sigmoid_forward_backward else []:
-        shards = [rows(n, d, 1000 * n + d + 101 * r).to(dev) for r in range(W)]
-        loss, grads, dtau, dbias = emulated_sigmoid_forward_backward(shards, SIG_TAU, SIG_BIAS, compute=comp, grad_out=0.7)
-        print(f"sigmoid_dist W={W} n={n} d={d} {comp}: loss {digest(loss)} dtau {digest(dtau)} dbias {digest(dbias)} " +
-              " ".join(f"dh{r} {digest(g)}" for r, g in enumerate(grads)))
+    exchanges = [("sigmoid_dist", {})] if emulated_sigmoid_forward_backward else []
+    if exchanges and "exchange" in inspect.signature(emulated_sigmoid_forward_backward).parameters:
+        exchanges.append(("sigmoid_ring", {"exchange": "ring"}))
+    for name, kw in exchanges:
+        for W, n, d, comp in DIST:
+            shards = [rows(n, d, 1000 * n + d + 101 * r).to(dev) for r in range(W)]
+            loss, grads, dtau, dbias = emulated_sigmoid_forward_backward(shards, SIG_TAU, SIG_BIAS, compute=comp,
+                                                                         grad_out=0.7, **kw)
+            print(f"{name} W={W} n={n} d={d} {comp}: loss {digest(loss)} dtau {digest(dtau)} dbias {digest(dbias)} " +
+                  " ".join(f"dh{r} {digest(g)}" for r, g in enumerate(grads)))
     torch.cuda.synchronize()
 
 
