@@ -22,5 +22,7 @@ from .ops import (  # noqa: F401,E402
     info_nce_loss,
     ntxent_loss,
     positive_rank,
+    retrieval_metrics,
+    retrieval_rank,
     sigmoid_loss,
 )

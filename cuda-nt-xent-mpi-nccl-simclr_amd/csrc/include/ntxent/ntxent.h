@@ -450,6 +450,25 @@ void launch_small_bwd(DType in, DType comp, const void* zq, const void* h, const
 void launch_pos_rank(DType comp, const void* zq, const Geometry& g, int* rank, float* pos_cos, float* hard_neg_cos,
                      hipStream_t stream);
 
+// ---- cross-view retrieval ranks (kernels/xview_rank_kernels.hip) --------------------------
+// In-batch two-tower retrieval on one rank's rows (g.world == 1; g's temperature plays no part).
+// zq: launch_prep's unit rows [rows_pad][ld_k] in `comp` (fp32, fp16 or bf16), a_i = zq_i and
+// b_i = zq_(n + i), n = R / 2, S_ij the fp32 MFMA dot of a_i and b_j. In stacked order (entry i:
+// a_i ranked among the n rows of b; entry n + i: b_i ranked among the n rows of a):
+//   pos_cos[i] = pos_cos[n + i] = t_i = <a_i, b_i>
+//   rank[i]     = #{ j != i : S_ij > t_i },  rank[n + i] = #{ j != i : S_ji > t_i }   (strict)
+//   hard_neg_cos[.]   = the largest S over the same n - 1 candidates (-inf when n == 1)
+//   hard_neg_index[.] = the lowest pair index j in [0, n) that attains it (-1 when n == 1): the
+//                       candidate's place within the OTHER view
+// The N x N block Z1 Z2^T in 128 x 128 MFMA tiles, each computed once for both directions; its
+// epilogue compares and counts, no N^2 data is stored. The four outputs ([R] each) need no
+// initialisation, and neither does key_scratch (xview_rank_scratch_bytes, 8-byte aligned); counts
+// and maxima are merged with integer atomics only, so the result is bitwise repeatable in any
+// arrival order. Three launches, no host sync: capturable. Opt-in: no training step calls it.
+size_t xview_rank_scratch_bytes(const Geometry& g);
+void launch_xview_rank(DType comp, const void* zq, const Geometry& g, int* rank, float* pos_cos, float* hard_neg_cos,
+                       int* hard_neg_index, void* key_scratch, hipStream_t stream);
+
 // ---- cross-view InfoNCE (kernels/xview_kernels.hip) --------------------------------------
 // The CLIP-form two-tower loss of one rank's rows (g.world == 1): a row's columns are the rows of
 // the OTHER view only, the positive p(i) = (i + R/2) mod R included,

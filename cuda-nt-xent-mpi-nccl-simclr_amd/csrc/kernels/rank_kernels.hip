@@ -25,6 +25,7 @@
 #include "device_common.h"
 #include "pair_mask.h"
 #include "host_common.h"
+#include "rank_common.h"
 #include "tile128.h"
 
 namespace ntxent {
@@ -42,25 +43,6 @@ struct RankParams {
   float* pos;       // [R]
   int* hard;        // [R] hard_neg_cos, as its integer image until pos_rank_finish
 };
-
-// Order-preserving integer image of a float (signed compare): negative floats are mirrored.
-__device__ __forceinline__ int f2ord(float x) {
-  const int b = __float_as_int(x);
-  return b >= 0 ? b : b ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ord2f(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
-
-template <int CTRL> __device__ __forceinline__ int dpp_i(int x) {
-  return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, true);
-}
-// sum over the 16 lanes of a DPP row (every lane gets it)
-__device__ __forceinline__ int row16_isum(int x) {
-  x += dpp_i<0x128>(x);
-  x += dpp_i<0x124>(x);
-  x += dpp_i<0x122>(x);
-  x += dpp_i<0x121>(x);
-  return x;
-}
 
 // ---- prologue: positive cosines and output initialisation -------------------------------
 // One wave per pair (i, i + N); lane l sums the 16-byte chunks l, l + 64, ... of the two rows.

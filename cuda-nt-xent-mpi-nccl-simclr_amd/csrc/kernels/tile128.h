@@ -1,5 +1,5 @@
 // The 128 x 128 MFMA tile loop of the positive-rank and cross-view kernels (rank_kernels.hip,
-// xview_kernels.hip): acc = A B^T over K-major operand rows, one tile per workgroup. 4 waves, 64 x 64
+// xview_kernels.hip, xview_rank_kernels.hip): acc = A B^T over K-major operand rows, one tile per workgroup. 4 waves, 64 x 64
 // each (4 x 4 MFMA blocks of 16 x 16), fp32 accumulators; both operands staged 128 B of K per row
 // per step by global_load_lds into a double-buffered, XOR-swizzled LDS image. Device code only.
 #pragma once

@@ -299,6 +299,38 @@ std::vector<at::Tensor> positive_rank(const at::Tensor& h, const std::string& co
   return pos_rank(st[0], *P);
 }
 
+// Cross-view retrieval ranks, stage level: zq = prep's unit rows of a world-1 plan. Returns {rank
+// int32 [R], pos_cos fp32 [R], hard_neg_cos fp32 [R], hard_neg_index int32 [R]} in stacked order
+// (launch_xview_rank). The keys' scratch is allocated per call: the caching allocator orders its
+// reuse on the stream.
+std::vector<at::Tensor> xview_rank(const at::Tensor& zq, const Plan& P) {
+  check_input(zq, "zq");
+  NTXENT_CHECK(P.g.world == 1, "xview_rank: one rank only (a plan with world == 1)");
+  NTXENT_CHECK(zq.numel() == (long)P.g.rows_pad * P.g.ld_k && zq.scalar_type() == to_scalar(P.bwd()),
+               "zq must be [rows_pad, ld_k] in the plan's backward dtype");
+  const at::DeviceGuard guard(zq.device());
+  auto rank = at::empty({P.g.rows}, opts(zq, at::kInt));
+  auto pos = at::empty({P.g.rows}, opts(zq, at::kFloat));
+  auto hard = at::empty({P.g.rows}, opts(zq, at::kFloat));
+  auto index = at::empty({P.g.rows}, opts(zq, at::kInt));
+  auto keys = at::empty({(long)(xview_rank_scratch_bytes(P.g) / 8)}, opts(zq, at::kLong));
+  launch_xview_rank(P.bwd(), zq.data_ptr(), P.g, rank.data_ptr<int>(), pos.data_ptr<float>(), hard.data_ptr<float>(),
+                    index.data_ptr<int>(), keys.data_ptr(), cur_stream(zq));
+  return {rank, pos, hard, index};
+}
+
+// Cross-view retrieval ranks of stacked views h = [h1; h2] on the current stream: the row prologue
+// and xview_rank. Arguments and checks as positive_rank.
+std::vector<at::Tensor> retrieval_rank(const at::Tensor& h, const std::string& compute, bool use_mixed_precision) {
+  check_input(h, "h");
+  check_stacked(h);
+  const at::DeviceGuard guard(h.device());
+  const DType comp = backward_dtype(choose_compute(h.scalar_type(), use_mixed_precision, compute));
+  auto P = get_plan((int)h.size(0), (int)h.size(1), 1, 0, 1.0, dtype_name(comp), h.device().index());
+  const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
+  return xview_rank(st[0], *P);
+}
+
 // ---- cross-view InfoNCE (kernels/xview_kernels.hip) -----------------------------------------
 // The CLIP-form loss of stacked views h = [h1; h2] on the current stream: the row prologue, the
 // N x N tile GEMM with its LSE epilogue and the LSE merge. The compute dtype resolves as
@@ -1690,6 +1722,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(rank, pos_cos, hard_neg_cos) of stacked views h = [h1; h2] on the current stream: rank[i] counts the "
         "negatives whose cosine is strictly larger than the positive's. compute: auto|fp32|fp16|bf16|fp8, "
         "resolved as for the loss; fp8 computes in fp16.");
+  m.def("xview_rank", &xview_rank, py::arg("zq"), py::arg("plan"),
+        "Stage op: (rank, pos_cos, hard_neg_cos, hard_neg_index) of prep's unit rows zq for a world-1 plan, each "
+        "view's rows ranked among the other view's.");
+  m.def("retrieval_rank", &retrieval_rank, py::arg("h"), py::arg("compute") = "auto",
+        py::arg("use_mixed_precision") = false,
+        "(rank, pos_cos, hard_neg_cos, hard_neg_index) of stacked views h = [h1; h2] on the current stream: entry i "
+        "ranks view-1 row i among view 2, entry N + i view-2 row i among view 1. compute as for positive_rank.");
   m.def("fwd_stats_range", &fwd_stats_range, py::arg("zq_local"), py::arg("zq_all"), py::arg("plan"), py::arg("part"),
         py::arg("sc"), py::arg("first"), py::arg("count"), py::arg("reserve_cus") = 0);
   m.def("fwd_stats", [](const at::Tensor& zl, const at::Tensor& za, const Plan& P, bool keep) {

@@ -22,7 +22,7 @@ from typing import Optional
 import torch
 
 from . import _ext, reference
-from .ntxent import (_reference_loss, _stack_views, _tau_grad, _tau_like, _TemperatureModule, _use_reference,
+from .ntxent import (_reference_loss, _stack_views, _tau_grad, _tau_like, _CrossViewModule, _use_reference,
                      resolve_compute, temperature_value, temperature_wants_grad)
 
 
@@ -79,7 +79,7 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
     return InfoNCEFunction.apply(h, temperature_value(temperature), comp, tau)
 
 
-class InfoNCELoss(_TemperatureModule):
+class InfoNCELoss(_CrossViewModule):
     """``nn.Module`` front end: ``InfoNCELoss(temperature)(z1, z2)`` or ``(h)``. One GPU
     (``parallel.DistInfoNCELoss`` for the data-parallel batch).
 

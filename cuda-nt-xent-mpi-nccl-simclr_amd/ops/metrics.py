@@ -10,6 +10,10 @@ On the GPU the rank comes from a kernel of its own (``csrc/kernels/rank_kernels.
 prologue, then a similarity GEMM over the upper-triangular tiles whose epilogue compares and
 counts; no 2N x 2N data is stored. The launch is opt-in: nothing in the loss, its backward or
 the timed training step calls it, and it reads none of their buffers.
+
+The two-tower losses (InfoNCE, sigmoid) contrast a row against the other view only; their metrics are
+``retrieval_rank`` / ``retrieval_metrics``: each view ranked among the ``N`` rows of the other, with
+the hardest in-batch negative and its index (``csrc/kernels/xview_rank_kernels.hip``).
 """
 from __future__ import annotations
 
@@ -81,4 +85,73 @@ def contrastive_metrics(h: torch.Tensor, *, z2: Optional[torch.Tensor] = None, t
         out["pos_cos"] = pos.mean()
         out["hard_neg_cos"] = hard.mean()
         out["negatives"] = torch.full((), rank.numel() - 2, dtype=torch.int64, device=rank.device)
+    return out
+
+
+def retrieval_rank(h: torch.Tensor, *, z2: Optional[torch.Tensor] = None, compute: str = "auto",
+                   use_mixed_precision: bool = False
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``(rank, pos_cos, hard_neg_cos, hard_neg_index)`` of stacked views ``h = [h1; h2]`` (or
+    ``h1=h, z2=h2``): in-batch two-tower retrieval, each row ranked among the ``N`` rows of the
+    OTHER view only, as the cross-view losses (``info_nce_loss``, ``sigmoid_loss``) contrast it.
+
+    With ``a_i`` / ``b_i`` the L2-normalised rows of view 1 / view 2 and ``t_i = <a_i, b_i>``, in
+    stacked order (entry ``i``: view-1 row ``i`` among view 2; entry ``N + i``: view-2 row ``i``
+    among view 1; the two directions differ):
+      rank[i]           int32: ``#{ j != i : <a_i, b_j> > t_i }``, strictly; 0 means the partner is
+                        retrieved first. ``rank[N + i] = #{ j != i : <b_i, a_j> > t_i }``
+      pos_cos[i]        fp32: ``t_i`` (the same in both halves)
+      hard_neg_cos[i]   fp32: the largest cosine among the row's ``N - 1`` negatives (``-inf`` when
+                        ``N == 1``)
+      hard_neg_index[i] int32: the pair index ``j`` in ``[0, N)`` of that hardest negative within the
+                        other view, the lowest on an exact tie (``-1`` when ``N == 1``)
+
+    On the GPU one kernel family (``csrc/kernels/xview_rank_kernels.hip``) computes every
+    128 x 128 tile of ``Z1 Z2^T`` once for both directions; no ``N x N`` data is stored and the
+    result is bitwise repeatable. Arguments, ``no_grad`` and the CPU / reference path as
+    :func:`positive_rank`.
+    """
+    with torch.no_grad():
+        h = _stack(h, z2)
+        comp = resolve_compute(h.dtype, use_mixed_precision, compute)
+        if _use_reference(h):
+            if h.is_cuda and os.environ.get("NTXENT_ALLOW_REFERENCE", "0") != "1":
+                raise RuntimeError("NTXENT_FORCE_REFERENCE requires NTXENT_ALLOW_REFERENCE=1")
+            rank, pos, hard, index = reference.retrieval_rank(h)
+            return rank, pos.float(), hard.float(), index
+        rank, pos, hard, index = _ext.load().retrieval_rank(h.contiguous(), comp, False)
+        return rank, pos, hard, index
+
+
+def retrieval_metrics(h: torch.Tensor, *, z2: Optional[torch.Tensor] = None, topk: Sequence[int] = (1, 5, 10),
+                      compute: str = "auto", use_mixed_precision: bool = False) -> Dict[str, torch.Tensor]:
+    """In-batch retrieval recall and friends of stacked views, as 0-d tensors on the device of ``h``:
+
+      ``top{k}_1to2``  R@k of view 1 -> view 2: fraction of view-1 rows whose partner is among the k
+                       most similar view-2 rows (``rank < k``)
+      ``top{k}_2to1``  R@k of view 2 -> view 1
+      ``top{k}``       the mean of the two directions
+      ``mean_rank``    mean of ``rank`` over both directions
+      ``pos_cos``      mean cosine of the pairs
+      ``hard_neg_cos`` mean over the rows of the largest negative cosine
+      ``negatives``    ``N - 1``, the negatives each row is ranked against (int64)
+
+    Derived from :func:`retrieval_rank`'s integer ``rank`` (no host sync here). Arguments as for
+    :func:`retrieval_rank`.
+    """
+    ks = [int(k) for k in topk]
+    if any(k < 1 for k in ks):
+        raise ValueError("topk entries must be >= 1")
+    rank, pos, hard, _ = retrieval_rank(h, z2=z2, compute=compute, use_mixed_precision=use_mixed_precision)
+    with torch.no_grad():
+        n = rank.numel() // 2
+        out = {}
+        for k in ks:
+            hit = (rank < k).float()
+            out[f"top{k}_1to2"], out[f"top{k}_2to1"] = hit[:n].mean(), hit[n:].mean()
+            out[f"top{k}"] = hit.mean()
+        out["mean_rank"] = rank.float().mean()
+        out["pos_cos"] = pos.mean()
+        out["hard_neg_cos"] = hard.mean()
+        out["negatives"] = torch.full((), n - 1, dtype=torch.int64, device=rank.device)
     return out

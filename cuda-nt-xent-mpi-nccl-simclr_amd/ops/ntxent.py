@@ -136,6 +136,21 @@ class _TemperatureModule(torch.nn.Module):
         return f", learnable_temperature=True, temperature_bounds={self.temperature_bounds}"
 
 
+class _CrossViewModule(_TemperatureModule):
+    """What the two-tower losses (InfoNCELoss, SigmoidLoss) add: in-batch retrieval metrics."""
+
+    def retrieval_metrics(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None, topk=(1, 5, 10)):
+        """In-batch retrieval metrics of the same inputs ``forward`` takes
+        (``ops.metrics.retrieval_metrics``: ``top{k}_1to2``, ``top{k}_2to1``, ``top{k}``, ``mean_rank``,
+        ``pos_cos``, ``hard_neg_cos``, ``negatives``) with the module's ``compute`` and
+        ``use_mixed_precision``: each row is ranked among the ``N`` rows of the other view only, as
+        these losses contrast it. No gradient, and independent of the temperature."""
+        from .metrics import retrieval_metrics
+
+        return retrieval_metrics(z1, z2=z2, topk=topk, compute=self.compute,
+                                 use_mixed_precision=self.use_mixed_precision)
+
+
 class NTXentFunction(torch.autograd.Function):
     """loss = NTXent(h) for stacked views h = [h1; h2] on one GPU.
 

@@ -241,6 +241,49 @@ def positive_rank(h: torch.Tensor):
 
 
 # ---------------------------------------------------------------------------------------
+# Cross-view retrieval: each row ranked among the N rows of the other view only.
+# ---------------------------------------------------------------------------------------
+def _retrieval_block(z_unit: torch.Tensor):
+    """(S, t, keep) of unit rows [2N, d]: S = Z1 Z2^T, its diagonal t (the pairs' cosines) and the
+    [N, N] mask of the negatives (everything but the diagonal)."""
+    if z_unit.dim() != 2 or z_unit.shape[0] % 2 or z_unit.shape[0] == 0:
+        raise ValueError("expected stacked views [2N, d]")
+    n = z_unit.shape[0] // 2
+    S = z_unit[:n] @ z_unit[n:].t()
+    return S, S.diagonal().clone(), ~torch.eye(n, dtype=torch.bool, device=z_unit.device)
+
+
+def retrieval_rank_bounds(z_unit: torch.Tensor, delta: float):
+    """(lo, hi) for unit rows ``z_unit`` ([2N, d], used as they are), stacked order: entry ``i``
+    counts the view-2 candidates ``j != i`` with ``<a_i, b_j> > t_i + delta`` (``lo``) or ``> t_i -
+    delta`` (``hi``), entry ``N + i`` the view-1 candidates with ``<b_i, a_j>`` likewise. An
+    implementation whose cosines are all within ``delta / 2`` of these has ``lo <= rank <= hi``."""
+    S, t, keep = _retrieval_block(z_unit)
+    both = torch.cat([S, S.t()], 0)  # row N + i: column i of S
+    t2, keep2 = torch.cat([t, t]).unsqueeze(1), torch.cat([keep, keep], 0)
+    return ((both > t2 + delta) & keep2).sum(1), ((both > t2 - delta) & keep2).sum(1)
+
+
+def retrieval_rank(h: torch.Tensor):
+    """(rank int32 [2N], pos_cos [2N], hard_neg_cos [2N], hard_neg_index int32 [2N]) of stacked
+    views ``h = [h1; h2]``, in the dtype of ``h`` and in stacked order: entry ``i`` ranks view-1
+    row ``i`` among view 2, entry ``N + i`` view-2 row ``i`` among view 1. ``rank`` counts the other
+    view's ``N - 1`` negatives whose cosine is strictly above the pair's; ``hard_neg_cos`` is the
+    largest of them and ``hard_neg_index`` the lowest pair index that attains it (``-inf`` and
+    ``-1`` when ``N == 1``)."""
+    z, _ = normalize(h)
+    S, t, keep = _retrieval_block(z)
+    n = S.shape[0]
+    lo, _ = retrieval_rank_bounds(z, 0.0)
+    both = torch.cat([S, S.t()], 0).masked_fill(~torch.cat([keep, keep], 0), float("-inf"))
+    hard = both.max(1).values
+    # the lowest index of the maximum (argmax does not promise which of several it returns)
+    cand = torch.arange(n, device=h.device).expand_as(both).masked_fill(both != hard.unsqueeze(1), n)
+    index = cand.min(1).values if n > 1 else torch.full((2 * n,), -1, device=h.device)
+    return lo.to(torch.int32), torch.cat([t, t]), hard, index.to(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------
 # Data-parallel layout: rank r holds h_r = [h1_r; h2_r] (2n rows); positives are rank-local.
 # ---------------------------------------------------------------------------------------
 def global_pair_order(shards: Sequence[torch.Tensor]) -> torch.Tensor:

@@ -25,7 +25,7 @@ from typing import Optional
 import torch
 
 from . import _ext, reference
-from .ntxent import (_stack_views, _tau_grad, _tau_like, _TemperatureModule, _use_reference, resolve_compute,
+from .ntxent import (_stack_views, _tau_grad, _tau_like, _CrossViewModule, _use_reference, resolve_compute,
                      temperature_wants_grad)
 
 
@@ -114,7 +114,7 @@ def sigmoid_loss(h: torch.Tensor, temperature=0.1, bias=-10.0, *, z2: Optional[t
     return SigmoidFunction.apply(h, tv, bv, comp, tau, bias_t)
 
 
-class SigmoidLoss(_TemperatureModule):
+class SigmoidLoss(_CrossViewModule):
     """``nn.Module`` front end: ``SigmoidLoss(temperature, bias)(z1, z2)`` or ``(h)``. One GPU.
 
     ``learnable_temperature=True``: as ``InfoNCELoss``, an fp32 parameter ``log_temperature``
