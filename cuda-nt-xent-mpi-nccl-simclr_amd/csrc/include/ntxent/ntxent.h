@@ -496,7 +496,8 @@ void launch_xview_fwd(DType comp, const void* zq, float* ypos, const Geometry& g
 //     block G = P12 + P21^T - 2 I into `coef` (xview_coef_bytes), written once: one fp32 plane for
 //     fp32 plans; for 16-bit plans two planes in the compute dtype, G rounded to it and the scaled
 //     residual of that rounding, so the MFMA operands carry about twice the dtype's mantissa.
-//     4 N_pad^2 bytes in every plan: the only N^2 data.
+//     4 N_pad^2 bytes in every plan: the only N^2 data (of this, the stored backward; the fused
+//     backward below has none).
 //   launch_xview_dz: G Z2, G -> G^T in place in `coef`, then G^T Z1, on MFMA into the fp32 slab
 //     `dz` (xview_dz_bytes: [rows_pad][dim_n], rows < R and columns < roundup(dim_k, 128) written).
 // No buffer needs initialisation; no host sync, no atomics: deterministic and capturable.
@@ -506,6 +507,19 @@ size_t xview_dz_bytes(const Geometry& g);
 void launch_xview_coef(DType comp, const void* zq, const float* lse2, const float* cpos, const Geometry& g, void* coef,
                        void* zt, hipStream_t stream);
 void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, float* dz, hipStream_t stream);
+// The fused backward, rank g.rank of g.world (one GPU: world 1, zq_all = zq, lse2_all = lse2): after
+// launch_xview_dist_zt (kslots = g.world) ONE launch recomputes every 128 x 128 tile of S, forms the
+// tile of G in registers with the stored block's arithmetic, passes it through LDS and feeds it to
+// the dZ MFMA, both sides at once: no `coef`, O(N d) memory, no transpose of G and no second
+// coefficient pass. dz: col_splits fp32 slabs [rows_pad][dim_n] (xview_fused_dz_bytes), one per
+// split of a side's column tiles, for launch_norm_bwd(nslabs = col_splits). col_splits 0: the
+// smallest power of two, at most 4, that gives every CU a workgroup (never more than the column
+// tiles); both functions resolve 0 alike, for the current device. Feature rows wider than 256 are
+// served in chunks of 256 columns, each of which recomputes S. No buffer needs initialisation; no
+// host sync, no atomics: bitwise repeatable and capturable.
+size_t xview_fused_dz_bytes(const Geometry& g, int col_splits);
+void launch_xview_fused_bwd(DType comp, const void* zq_all, const float* lse2_all, const float* cpos, const Geometry& g,
+                            const void* zt, float* dz, int col_splits, hipStream_t stream);
 
 // ---- pairwise sigmoid loss, the SigLIP form (kernels/xview_kernels.hip) -------------------------------
 // One GPU (g.world == 1), zq = launch_prep's unit rows of the stacked views, n = R/2 pairs:

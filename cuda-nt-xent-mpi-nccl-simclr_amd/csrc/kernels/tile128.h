@@ -98,6 +98,37 @@ __device__ __forceinline__ void tile128_gemm(lds_char* lds, int nsteps, AAt a_at
   if constexpr (kEndBarrier) __syncthreads();  // every wave is done with the staging images
 }
 
+// The loop form whose A images are already resident in LDS (the caller wrote them: a tile formed in
+// registers): only B is staged, so the whole staging area `ring` (kTile128Lds bytes) is a ring of four
+// B images and step t + 2 is in flight while step t multiplies. Steps t in [0, nsteps), ascending,
+// nsteps <= kSteps (block-uniform); b_at(t) is the Tile128Src of step t's B rows and step(t, bimg)
+// multiplies: the caller picks the resident A image and the accumulators of step t, and since the
+// loop is unrolled over kSteps, t is a constant there (accumulator arrays stay in registers). The
+// first barrier also publishes the caller's LDS writes of the A images. Ends with a block barrier:
+// every wave is done with the ring and with the A images.
+template <int kSteps, class BAt, class Step>
+__device__ __forceinline__ void tile128_gemm_resident_a(lds_char* ring, int nsteps, BAt b_at, Step step) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  tile128_stage(b_at(0), ring, w, lane);
+  if (nsteps > 1) tile128_stage(b_at(1), ring + kTile128Stage, w, lane);
+#pragma unroll
+  for (int t = 0; t < kSteps; ++t) {
+    if (t < nsteps) {
+      // step t landed for this wave (a stage is 4 loads per lane: step t + 1's may stay in flight);
+      // the barrier makes it visible to every wave and orders every wave's reads of step t - 2
+      // before that slot is restaged
+      if (t + 1 < nsteps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (t + 2 < nsteps) tile128_stage(b_at(t + 2), ring + ((t + 2) & 3) * kTile128Stage, w, lane);
+      step(t, (const lds_char*)(ring + (t & 3) * kTile128Stage));
+    }
+  }
+  __syncthreads();
+}
+
 // No work between the steps: the on_step of a plain product.
 struct Tile128Plain {
   __device__ __forceinline__ void operator()(int, f32x4 (&)[4][4]) const {}

@@ -31,7 +31,8 @@
 //                       of that rounding, so that the MFMA operands carry the coefficients to about
 //                       twice the dtype's mantissa (a gradient of equal coefficients is otherwise off
 //                       by the dtype's rounding of that one number). The only n N data, 4 n_pad W n_pad
-//                       bytes in every plan. Side 1 swaps the operand roles and so gives the rows of
+//                       bytes in every plan, and only of the stored backward: xview_fused_bwd_kernel
+//                       (below, after xview_dz_kernel) forms the same tiles of G and never stores them. Side 1 swaps the operand roles and so gives the rows of
 //                       G^T directly.
 //   xview_transpose_kernel : Zt[v][e][q n_pad + c] = zq[q rows_pad + v n + c][e] for every slot q,
 //                       both views aligned at column 0 of their slot and zero padded to n_pad columns
@@ -305,19 +306,61 @@ __global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double*
   }
 }
 
+// ---- backward: the G step, from a tile of S in tile128.h's accumulator layout to the tile of G ------
+// InfoNCE's: G_ij = exp2(y_ij - lse2_i) + exp2(y_ij - lse2_j) from the own and the gathered lse2, cpos
+// on the positives of the own slot, zero for rows and columns at or beyond n of their slot. emit(rt,
+// ct, v): element (rt, ct) of the 128 x 128 tile, each once. Both backwards call this one function
+// (the stored block's kernel and the fused kernel), so their coefficients are the same bits; another
+// loss's G step is another functor of this shape.
+struct XvInfoNceG {
+  template <class Emit>
+  __device__ __forceinline__ void operator()(const XvParams& p, int side, int I, int q, int Jl,
+                                             const f32x4 (&acc)[4][4], Emit emit) const {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+    const int n = p.n;
+    const bool own = q == p.rank;
+    const float* lrow = p.lse2 + (long long)p.rank * p.rows_pad + side * n;
+    const float* lcol = p.lse2 + (long long)q * p.rows_pad + (1 - side) * n;
+    int cl[4];
+    float lc[4];
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+      lc[ni] = cl[ni] < n ? lcol[cl[ni]] : 0.f;
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rt = 64 * wr + 16 * mi + 4 * g + r;
+        const int li = I * kXvTile + rt;
+        const float lr = li < n ? lrow[li] : 0.f;
+        const float cp = li < n ? p.cpos[side * n + li] : 0.f;
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          const float y = acc[mi][ni][r] * p.scale2;
+          const bool ok = (li < n) & (cl[ni] < n);
+          const float c = fast_exp2(y - lr) + fast_exp2(y - lc[ni]);
+          // selects, not products: outside the valid rows and columns the exponentials may overflow
+          const float v = ok ? ((own & (cl[ni] == li)) ? cp : c) : 0.f;
+          emit(rt, 64 * wc + 16 * ni + r16, v);
+        }
+      }
+  }
+};
+
 // ---- backward: tile (I, J) of one side's n_pad x W n_pad block G, stored once ----------------------
 template <typename T>
 __global__ __launch_bounds__(kXvThreads) void xview_side_coef_kernel(const XvParams p) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int tid = threadIdx.x;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
   const int ncol = p.world * p.nT;
   const int I = b / ncol, J = b - I * ncol;
   const int q = J / p.nT, Jl = J - q * p.nT;
-  const int n = p.n, side = p.side;
-  const bool own = q == p.rank;
+  const int side = p.side;
 
   f32x4 acc[4][4];
   xv_tile_gemm<T>(p, side, I, q, Jl, lds, acc);
@@ -328,40 +371,16 @@ __global__ __launch_bounds__(kXvThreads) void xview_side_coef_kernel(const XvPar
   constexpr bool kSplit = sizeof(T) == 2;
   constexpr int kPlaneElems = kXvTile * kXvTile;
   T* s_g = reinterpret_cast<T*>(smem);
-  const float* lrow = p.lse2 + (long long)p.rank * p.rows_pad + side * n;
-  const float* lcol = p.lse2 + (long long)q * p.rows_pad + (1 - side) * n;
-  int cl[4];
-  float lc[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
-    lc[ni] = cl[ni] < n ? lcol[cl[ni]] : 0.f;
-  }
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rt = 64 * wr + 16 * mi + 4 * g + r;
-      const int li = I * kXvTile + rt;
-      const float lr = li < n ? lrow[li] : 0.f;
-      const float cp = li < n ? p.cpos[side * n + li] : 0.f;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const float y = acc[mi][ni][r] * p.scale2;
-        const bool ok = (li < n) & (cl[ni] < n);
-        const float c = fast_exp2(y - lr) + fast_exp2(y - lc[ni]);
-        // selects, not products: outside the valid rows and columns the exponentials may overflow
-        const float v = ok ? ((own & (cl[ni] == li)) ? cp : c) : 0.f;
-        const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
-        const T hi = from_f32<T>(v);
-        if constexpr (kSplit) {
-          s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
-          s_g[kPlaneElems + at] = hi;
-        } else {
-          s_g[at] = hi;
-        }
-      }
+  XvInfoNceG{}(p, side, I, q, Jl, acc, [&](int rt, int ct, float v) __attribute__((always_inline)) {
+    const int at = rt * kXvTile + ct;
+    const T hi = from_f32<T>(v);
+    if constexpr (kSplit) {
+      s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
+      s_g[kPlaneElems + at] = hi;
+    } else {
+      s_g[at] = hi;
     }
+  });
   __syncthreads();
   // 16-byte chunks, rows contiguous: 8 * sizeof(T) chunks per row, 4096 chunks in all
   constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
@@ -495,6 +514,149 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
         }
       }
     }
+}
+
+// ---- fused backward: out = G Z without G in memory ---------------------------------------------------
+// A workgroup owns 128 rows of one side (row tile I), an e-chunk of kXvFuseChunk feature columns and a
+// contiguous share [j0, j1) of the side's W nT column tiles (slots q ascending, then Jl ascending). For
+// each column tile of the share, in order:
+//   1. S_IJ by xv_tile_gemm (the staging ring, 64 KiB) into acc;
+//   2. the tile of G from acc by the G step (XvInfoNceG: the stored block's arithmetic, the same bits);
+//   3. G into LDS as tile128_mma_step's A images, K along the tile's 128 columns, 64 KiB beside the
+//      ring (one __shared__ object of 128 KiB): fp32 plans four K-steps of one plane; 16-bit plans two
+//      K-steps of the residual plane (G - hi) * kXvLoScale and two of hi = G rounded to T;
+//   4. per 128-wide sub-tile of the e-chunk the rows of zt[1 - side] through the ring as B
+//      (tile128_gemm_resident_a) into accumulators that stay in registers over the whole share. 16-bit
+//      plans: a B K-step multiplies both planes, the residual plane's products into a 64-register
+//      temporary that is scaled back (a power of two: exact) and added once the tile's two K-steps are
+//      done, so the coefficients reach the MFMA at about twice the dtype's mantissa as the stored
+//      planes do.
+// Split s of kc writes its own fp32 slab dz[s][rows_pad][ldo]; launch_norm_bwd sums the slabs in a
+// fixed order. Every output element is one workgroup's fixed-order sum: bitwise repeatable, no
+// atomics, no buffer that needs initialisation. O(N d) memory: G never leaves the CU.
+// e-chunk: 256 columns, two sub-tiles = 128 accumulator registers per lane, chosen from the compiler's
+// resource report (gfx950, -O3, -Rpass-analysis=kernel-resource-usage): fp32 249 VGPRs + 192 AGPRs,
+// fp16 and bf16 250 + 256, no scratch and no vector spill in any of them, one wave per SIMD (the
+// 128 KiB of LDS allow one workgroup per CU anyway). 512 columns would need 128 more accumulators
+// than the 512 registers of a lane hold beside these. Rows wider than the chunk take
+// ceil(roundup(d, 128) / 256) chunks and every chunk recomputes S: the similarity GEMM's work once
+// per chunk (d = 2048: eight times, which measures 3.5x slower than the stored backward; d = 512:
+// twice, faster than it. BASELINE.md).
+constexpr int kXvFuseChunk = 256;
+constexpr int kXvFuseSubs = kXvFuseChunk / kXvTile;
+constexpr int kXvFuseLds = 2 * kTile128Lds;  // the staging ring, then the G images
+constexpr int kXvFuseMaxSplits = 4;
+
+struct XvFuseParams {
+  XvParams x;        // the tile GEMM's operands, lse2 and cpos (side: blockIdx.y)
+  const char* zt;    // [2][En][ldz bytes]
+  long long ldz;
+  int En;            // roundup(dim_k, 128)
+  int nec;           // e-chunks
+  int kc;            // column splits, <= world * nT
+  float* dz;         // [kc][rows_pad][ldo]
+  long long ldo;
+  long long slab;    // rows_pad * ldo
+};
+
+template <typename T, class GStep>
+__global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFuseParams pf) {
+  // ONE __shared__ object
+  __shared__ __attribute__((aligned(16))) char smem[kXvFuseLds];
+  typedef __attribute__((address_space(3))) T lds_T;
+  lds_char* ring = (lds_char*)smem;
+  lds_char* gimg = ring + kTile128Lds;
+  const XvParams& p = pf.x;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int side = blockIdx.y;
+  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const int s = b % pf.kc, be = b / pf.kc;
+  const int ec = be % pf.nec, I = be / pf.nec;
+  const int ncol = p.world * p.nT;
+  const int j0 = (int)((long long)s * ncol / pf.kc), j1 = (int)((long long)(s + 1) * ncol / pf.kc);
+  const int nsub = min(kXvFuseSubs, pf.En / kXvTile - ec * kXvFuseSubs);  // >= 1
+  constexpr bool kSplit = sizeof(T) == 2;
+  constexpr int kKs = kXvTile * (int)sizeof(T) / kKStepBytes;  // K-steps of a plane of the tile: 2 | 4
+
+  f32x4 out[kXvFuseSubs][4][4];
+#pragma unroll
+  for (int sub = 0; sub < kXvFuseSubs; ++sub)
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni) out[sub][mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // B: rows e of the OTHER view's Zt from the chunk's first sub-tile on; K along the columns
+  const char* bchunk = pf.zt + ((long long)(1 - side) * pf.En + (long long)ec * kXvFuseChunk) * pf.ldz;
+
+  for (int J = j0; J < j1; ++J) {
+    const int q = J / p.nT, Jl = J - q * p.nT;
+    {
+      f32x4 acc[4][4];
+      xv_tile_gemm<T>(p, side, I, q, Jl, ring, acc);  // ends with a barrier: the last tile's images are free
+      GStep{}(p, side, I, q, Jl, acc, [&](int rt, int ct, float v) __attribute__((always_inline)) {
+        const int kb = ct * (int)sizeof(T);  // byte along K
+        lds_char* at = gimg + (kb >> 7) * kTile128Stage + tile128_off(rt, (kb & 127) >> 4) + (kb & 15);
+        const T hi = from_f32<T>(v);
+        if constexpr (kSplit) {
+          *(lds_T*)at = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
+          *(lds_T*)(at + kKs * kTile128Stage) = hi;
+        } else {
+          *(lds_T*)at = hi;
+        }
+      });
+    }
+    // steps t = sub * kKs + k: the tile's K-steps for one e sub-tile after the other
+    const char* bcol = bchunk + (long long)J * kXvTile * (int)sizeof(T);
+    [[maybe_unused]] f32x4 lo[4][4];
+    tile128_gemm_resident_a<kXvFuseSubs * kKs>(
+        ring, nsub * kKs,
+        [&](int t) __attribute__((always_inline)) {
+          return Tile128Src{bcol + (long long)(t / kKs) * kXvTile * pf.ldz + (long long)(t % kKs) * kKStepBytes, pf.ldz};
+        },
+        [&](int t, const lds_char* bimg) __attribute__((always_inline)) {
+          const int sub = t / kKs, k = t % kKs;
+          if constexpr (kSplit) {
+            if (k == 0) {
+#pragma unroll
+              for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) lo[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            tile128_mma_step<T>(gimg + k * kTile128Stage, bimg, wr, wc, r16, g, lo);
+            tile128_mma_step<T>(gimg + (kKs + k) * kTile128Stage, bimg, wr, wc, r16, g, out[sub]);
+            if (k == kKs - 1) {  // the residual plane of this tile is done: back to G's scale
+#pragma unroll
+              for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni) out[sub][mi][ni] += lo[mi][ni] * (1.0f / kXvLoScale);
+            }
+          } else {
+            tile128_mma_step<T>(gimg + k * kTile128Stage, bimg, wr, wc, r16, g, out[sub]);
+          }
+        });
+  }
+
+  // rows of this view at or beyond n do not exist (the coefficients are zero there anyway)
+  float* slab = pf.dz + (long long)s * pf.slab;
+#pragma unroll
+  for (int sub = 0; sub < kXvFuseSubs; ++sub) {
+    if (sub < nsub) {
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+          if (m < p.n) {
+            float* orow = slab + ((long long)side * p.n + m) * pf.ldo + (long long)ec * kXvFuseChunk + sub * kXvTile +
+                          64 * wc + r16;
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) orow[16 * ni] = out[sub][mi][ni][r];
+          }
+        }
+    }
+  }
 }
 
 // ---- pairwise sigmoid loss (the SigLIP form) ---------------------------------------------------------
@@ -903,6 +1065,58 @@ void launch_xview_dz(DType comp, void* coef, const void* zt, const Geometry& g, 
                        static_cast<Tc*>(coef), (long long)np, (long long)np * np);
     q.side = 1;
     hipLaunchKernelGGL((dev::xview_dz_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, q);
+  });
+  NTXENT_HIP_CHECK(hipGetLastError());
+}
+
+// ---- fused backward (one GPU: world 1, rank 0; distributed: zq_all and lse2_all) ---------------------
+namespace {
+inline int xv_fuse_chunks(const Geometry& g) { return (xv_en(g) + dev::kXvFuseChunk - 1) / dev::kXvFuseChunk; }
+// The column splits: a function of the geometry and the CU count alone. The smallest power of two,
+// at most kXvFuseMaxSplits (which bounds the slabs: 4 of them stay below the coefficient block they
+// replace), that gives every CU a workgroup, and never more than the side's column tiles.
+int xv_fuse_splits(const Geometry& g, int col_splits) {
+  const int nT = xv_npad(g) / dev::kXvTile, ncol = g.world * nT;
+  if (col_splits > 0) {
+    NTXENT_CHECK(col_splits <= dev::kXvFuseMaxSplits && col_splits <= ncol,
+                 "xview_fused_bwd: col_splits in [1, min(4, column tiles)], or 0 for the rule");
+    return col_splits;
+  }
+  int dev_id = 0;
+  NTXENT_HIP_CHECK(hipGetDevice(&dev_id));
+  const int cus = device_info(dev_id).num_cus;
+  int kc = 1;
+  while (2 * kc <= dev::kXvFuseMaxSplits && 2 * kc <= ncol && 2 * nT * xv_fuse_chunks(g) * kc < cus) kc *= 2;
+  return kc;
+}
+}  // namespace
+
+size_t xview_fused_dz_bytes(const Geometry& g, int col_splits) {
+  return (size_t)xv_fuse_splits(g, col_splits) * xview_dz_bytes(g);
+}
+
+void launch_xview_fused_bwd(DType comp, const void* zq_all, const float* lse2_all, const float* cpos, const Geometry& g,
+                            const void* zt, float* dz, int col_splits, hipStream_t stream) {
+  NTXENT_CHECK(zq_all && lse2_all && cpos && zt && dz, "xview_fused_bwd: null buffer");
+  dev::XvFuseParams pf{};
+  pf.x = xv_params(comp, zq_all, g, "xview_fused_bwd");
+  pf.x.lse2 = lse2_all;
+  pf.x.cpos = cpos;
+  const size_t es = dtype_size(comp);
+  const int np = xv_npad(g), en = xv_en(g);
+  NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, "xview_fused_bwd: dim_n < roundup(dim_k, 128)");
+  pf.zt = static_cast<const char*>(zt);
+  pf.ldz = (long long)g.world * np * (long long)es;
+  pf.En = en;
+  pf.nec = xv_fuse_chunks(g);
+  pf.kc = xv_fuse_splits(g, col_splits);
+  pf.dz = dz;
+  pf.ldo = g.dim_n;
+  pf.slab = (long long)g.rows_pad * g.dim_n;
+  const dim3 grid(pf.x.nT * pf.nec * pf.kc, 2);
+  dispatch_comp(comp, [&](auto tc) {
+    hipLaunchKernelGGL((dev::xview_fused_bwd_kernel<decltype(tc), dev::XvInfoNceG>), grid, dim3(dev::kXvThreads), 0,
+                       stream, pf);
   });
   NTXENT_HIP_CHECK(hipGetLastError());
 }

@@ -375,13 +375,13 @@ static void check_xview_saved(const at::Tensor& inv, const at::Tensor& lse2_all,
 
 // The end of every backward (the callers release coef and zt before it: before dh exists): the
 // grad_out / (2N tau) scaling and the normalisation backward of the slab; dot: also
-// dot_i = z_i . (C z)_i, [rows].
+// dot_i = z_i . (C z)_i, [rows]. nslabs: the fused backward's column splits, one slab each.
 static at::Tensor xview_backward_tail(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& go,
                                       const at::Tensor& dz, const Geometry& g, hipStream_t stream,
-                                      at::Tensor* dot = nullptr) {
+                                      at::Tensor* dot = nullptr, int nslabs = 1) {
   auto dh = at::empty_like(h);
   if (dot) *dot = at::empty({g.rows}, opts(h, at::kFloat));
-  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), 1, h.data_ptr(), inv.data_ptr<float>(),
+  launch_norm_bwd(to_dtype(h.scalar_type()), dz.data_ptr<float>(), nslabs, h.data_ptr(), inv.data_ptr<float>(),
                   go.data_ptr<float>(), dh.data_ptr(), g, stream, nullptr, 0, dot ? dot->data_ptr<float>() : nullptr);
   return dh;
 }
@@ -395,6 +395,23 @@ static at::Tensor sigmoid_pos_cos(const at::Tensor& h, const at::Tensor& inv, DT
   launch_xview_sigmoid_pos(to_dtype(h.scalar_type()), h.data_ptr(), inv.data_ptr<float>(), g, pos.data_ptr<float>(),
                            cur_stream(h));
   return pos;
+}
+
+// The fused backward's middle (InfoNCE; launch_xview_fused_bwd): the transposes of the rows in
+// zq_all, then ONE launch into the column splits' slabs, which are returned with their count. No
+// coefficient block exists. zq_all may be released once this returns (stream-ordered).
+static at::Tensor xview_fused_dz(const Plan& P, const at::Tensor& ref, const void* zq_all, const at::Tensor& lse2_all,
+                                 const at::Tensor& cpos, int col_splits, hipStream_t stream, int* nslabs) {
+  const Geometry& g = P.g;
+  NTXENT_CHECK(col_splits >= 0, "col_splits must be >= 0 (0: the rule)");
+  auto zt = at::empty({(long)xview_zt_bytes(P.comp, g)}, opts(ref, at::kByte));
+  const size_t bytes = xview_fused_dz_bytes(g, col_splits);
+  *nslabs = (int)(bytes / xview_dz_bytes(g));
+  auto dz = at::empty({(long)(bytes / 4)}, opts(ref, at::kFloat));
+  launch_xview_dist_zt(P.comp, zq_all, g, g.world, zt.data_ptr(), stream);
+  launch_xview_fused_bwd(P.comp, zq_all, lse2_all.data_ptr<float>(), cpos.data_ptr<float>(), g, zt.data_ptr(),
+                         dz.data_ptr<float>(), *nslabs, stream);
+  return dz;
 }
 
 // The one-GPU backward of both losses, after the caller's checks: dh, and in *dtau (null: not wanted)
@@ -440,12 +457,31 @@ static at::Tensor xview_backward_body(const at::Tensor& h, const at::Tensor& inv
 // dtau as xview_backward_body's. compute: the forward's.
 static at::Tensor xview_backward_impl(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& lse2,
                                       const at::Tensor& cpos, const at::Tensor& grad_out, double T,
-                                      const std::string& compute, at::Tensor* dtau) {
+                                      const std::string& compute, at::Tensor* dtau, bool fused,
+                                      int col_splits) {
   check_input(h, "h");
   const at::DeviceGuard guard(h.device());
   auto P = xview_plan(h, T, backward_dtype(choose_compute(h.scalar_type(), false, compute)));
   check_xview_saved(inv, lse2, cpos, P->g,
                     "xview_backward: inv [rows], lse2 / cpos [rows_pad] in float32 (xview_forward's outputs)");
+  if (fused) {
+    // prep (again, as the stored path: see xview_backward_body), zt, the fused kernel, the tail
+    const hipStream_t stream = cur_stream(h);
+    const at::Tensor go = grad_scalar(grad_out);
+    int nslabs = 1;
+    at::Tensor dz;
+    {
+      const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
+      dz = xview_fused_dz(*P, h, st[0].data_ptr(), lse2, cpos, col_splits, stream, &nslabs);
+    }
+    at::Tensor dot;
+    auto dh = xview_backward_tail(h, inv, go, dz, P->g, stream, &dot, nslabs);
+    if (dtau) {
+      *dtau = at::empty({}, opts(h, at::kFloat));
+      launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau->data_ptr<float>(), P->g, stream);
+    }
+    return dh;
+  }
   return xview_backward_body(h, inv, grad_scalar(grad_out), *P, nullptr, dtau,
                              [&](void* zq, void* coef, void* zt, const float*, hipStream_t stream) {
                                launch_xview_coef(P->comp, zq, lse2.data_ptr<float>(), cpos.data_ptr<float>(), P->g, coef,
@@ -454,17 +490,17 @@ static at::Tensor xview_backward_impl(const at::Tensor& h, const at::Tensor& inv
 }
 
 at::Tensor xview_backward(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& lse2, const at::Tensor& cpos,
-                          const at::Tensor& grad_out, double T, const std::string& compute) {
-  return xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, nullptr);
+                          const at::Tensor& grad_out, double T, const std::string& compute, bool fused, int col_splits) {
+  return xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, nullptr, fused, col_splits);
 }
 
 // xview_backward plus the temperature gradient: (dh, dtau); dh is bitwise xview_backward's.
 std::tuple<at::Tensor, at::Tensor> xview_backward_tau(const at::Tensor& h, const at::Tensor& inv,
                                                       const at::Tensor& lse2, const at::Tensor& cpos,
                                                       const at::Tensor& grad_out, double T,
-                                                      const std::string& compute) {
+                                                      const std::string& compute, bool fused, int col_splits) {
   at::Tensor dtau;
-  auto dh = xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, &dtau);
+  auto dh = xview_backward_impl(h, inv, lse2, cpos, grad_out, T, compute, &dtau, fused, col_splits);
   return {dh, dtau};
 }
 
@@ -593,12 +629,18 @@ static at::Tensor xview_dist_backward_body(const at::Tensor& h, const at::Tensor
 
 at::Tensor xview_dist_backward(const at::Tensor& h, const at::Tensor& zq_all, const at::Tensor& inv,
                                const at::Tensor& lse2_all, const at::Tensor& cpos, const at::Tensor& grad_out,
-                               const Plan& P) {
+                               const Plan& P, bool fused, int col_splits) {
   check_h(h, P.g);
   check_xview_dist(zq_all, P);
   check_xview_saved(inv, lse2_all, cpos, P.g,
                     "xview_dist_backward: inv [rows], cpos [rows_pad], lse2_all [world*rows_pad] in float32");
   const at::DeviceGuard guard(h.device());
+  if (fused) {
+    int nslabs = 1;
+    const hipStream_t stream = cur_stream(h);
+    const at::Tensor dz = xview_fused_dz(P, h, zq_all.data_ptr(), lse2_all, cpos, col_splits, stream, &nslabs);
+    return xview_backward_tail(h, inv, grad_scalar(grad_out), dz, P.g, stream, nullptr, nslabs);
+  }
   return xview_dist_backward_body(h, zq_all, inv, grad_scalar(grad_out), P, nullptr, nullptr,
                                   [&](int side, void* coef, const float*, hipStream_t stream) {
                                     launch_xview_dist_coef(P.comp, zq_all.data_ptr(), lse2_all.data_ptr<float>(),
@@ -1805,8 +1847,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_backward", &fused_backward);
   m.def("fused_backward_tau", &fused_backward_tau);
   m.def("xview_forward", &xview_forward, py::arg("h"), py::arg("T"), py::arg("compute") = "auto");
-  m.def("xview_backward", &xview_backward);
-  m.def("xview_backward_tau", &xview_backward_tau);
+  m.def("xview_backward", &xview_backward, py::arg("h"), py::arg("inv"), py::arg("lse2"), py::arg("cpos"),
+        py::arg("grad_out"), py::arg("T"), py::arg("compute"), py::arg("fused") = false, py::arg("col_splits") = 0);
+  m.def("xview_backward_tau", &xview_backward_tau, py::arg("h"), py::arg("inv"), py::arg("lse2"), py::arg("cpos"),
+        py::arg("grad_out"), py::arg("T"), py::arg("compute"), py::arg("fused") = false, py::arg("col_splits") = 0);
   m.def("xview_sigmoid_forward", &xview_sigmoid_forward, py::arg("h"), py::arg("T"), py::arg("bias"),
         py::arg("compute") = "auto");
   m.def("xview_sigmoid_backward", &xview_sigmoid_backward);
@@ -1817,7 +1861,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xview_dist_lse", &xview_dist_lse, py::arg("part"), py::arg("ypos"), py::arg("lse2_all"), py::arg("cpos"),
         py::arg("plan"));
   m.def("xview_dist_backward", &xview_dist_backward, py::arg("h"), py::arg("zq_all"), py::arg("inv"),
-        py::arg("lse2_all"), py::arg("cpos"), py::arg("grad_out"), py::arg("plan"));
+        py::arg("lse2_all"), py::arg("cpos"), py::arg("grad_out"), py::arg("plan"), py::arg("fused") = false,
+        py::arg("col_splits") = 0);
   m.def("xview_sigmoid_dist_tiles", [](const Plan& P) { return (long)(xview_sigmoid_scratch_bytes(P.g) / 8); });
   m.def("xview_sigmoid_dist_fwd", &xview_sigmoid_dist_fwd, py::arg("zq_all"), py::arg("plan"), py::arg("lpart"),
         py::arg("h"), py::arg("inv"), py::arg("bias"), py::arg("q_lo"), py::arg("q_hi"), py::arg("q_skip") = -1);

@@ -13,7 +13,9 @@ whose epilogue reduces every tile to per-row and per-column LSE partials -> LSE 
 deterministic loss sum; backward: prep again -> the coefficient block ``G = P12 + P21^T - 2 I`` written
 once (fp32 plans in fp32; 16-bit plans as the rounded value plus the scaled residual of the rounding,
 two planes of the compute dtype) -> ``G Z2`` and ``G^T Z1`` on MFMA into an fp32 slab -> grad_out/(2N
-tau) scale + L2-normalisation backward (``csrc/kernels/xview_kernels.hip``).
+tau) scale + L2-normalisation backward (``csrc/kernels/xview_kernels.hip``). ``backward="fused"``
+never stores ``G``: one kernel recomputes each 128 x 128 tile of the similarities, forms the tile of
+``G`` in registers and feeds it through LDS into the dZ MFMA (O(N d) memory, five launches).
 """
 from __future__ import annotations
 
@@ -25,6 +27,15 @@ from . import _ext, reference
 from .ntxent import (_reference_loss, _stack_views, _tau_grad, _tau_like, _CrossViewModule, _use_reference,
                      resolve_compute, temperature_value, temperature_wants_grad)
 
+_BACKWARDS = ("stored", "fused")
+
+
+def _check_backward(backward: str, who: str) -> bool:
+    """Validate the ``backward`` keyword; True for the fused backward."""
+    if backward not in _BACKWARDS:
+        raise ValueError(f"{who}: backward must be one of {_BACKWARDS}, got {backward!r}")
+    return backward == "fused"
+
 
 class InfoNCEFunction(torch.autograd.Function):
     """loss = InfoNCE(h) for stacked views h = [h1; h2] on one GPU.
@@ -33,8 +44,10 @@ class InfoNCEFunction(torch.autograd.Function):
     then also returns dL/dtau (``xview_backward_tau``) in that tensor's dtype, shape and device."""
 
     @staticmethod
-    def forward(ctx, h: torch.Tensor, temperature: float, compute: str, tau: Optional[torch.Tensor] = None):
+    def forward(ctx, h: torch.Tensor, temperature: float, compute: str, tau: Optional[torch.Tensor] = None,
+                fused: bool = False):
         C = _ext.load()
+        ctx.fused = fused
         h = h.contiguous()
         loss, inv, lse2, cpos = C.xview_forward(h, float(temperature), compute)
         ctx.temperature = float(temperature)
@@ -48,14 +61,16 @@ class InfoNCEFunction(torch.autograd.Function):
         C = _ext.load()
         h, inv, lse2, cpos = ctx.saved_tensors
         if ctx.tau is None or not ctx.needs_input_grad[3]:
-            dh = C.xview_backward(h, inv, lse2, cpos, grad_out.reshape(1), ctx.temperature, ctx.compute)
-            return dh, None, None, None
-        dh, dtau = C.xview_backward_tau(h, inv, lse2, cpos, grad_out.reshape(1), ctx.temperature, ctx.compute)
-        return dh, None, None, _tau_grad(dtau, ctx.tau)
+            dh = C.xview_backward(h, inv, lse2, cpos, grad_out.reshape(1), ctx.temperature, ctx.compute,
+                                  fused=ctx.fused)
+            return dh, None, None, None, None
+        dh, dtau = C.xview_backward_tau(h, inv, lse2, cpos, grad_out.reshape(1), ctx.temperature, ctx.compute,
+                                        fused=ctx.fused)
+        return dh, None, None, _tau_grad(dtau, ctx.tau), None
 
 
 def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tensor] = None, compute: str = "auto",
-                  use_mixed_precision: bool = False) -> torch.Tensor:
+                  use_mixed_precision: bool = False, backward: str = "stored") -> torch.Tensor:
     """Cross-view InfoNCE of stacked views ``h = [h1; h2]`` (or ``h1=h, z2=h2``; the two may come from
     different encoders: autograd splits the gradient).
 
@@ -66,9 +81,15 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
       compute: ``auto|fp32|fp16|bf16|fp8``, resolved as for ``ntxent_loss``. ``fp8`` computes in
         fp16: these kernels have no fp8 operands (as the contrastive metrics).
       use_mixed_precision: fp32 inputs are computed in fp16 (fp32 accumulate) if True.
+      backward: ``"stored"`` writes the N x N coefficient block once and reads it back for the two dZ
+        products; ``"fused"`` never stores it (one kernel recomputes the similarities tile by tile and
+        feeds the coefficients to the dZ MFMA through LDS): O(N d) memory instead of 4 N^2 bytes, at
+        the price of one more similarity GEMM per 256 feature columns. The forward and the loss are
+        the same bits; the gradients agree to rounding.
 
     One GPU; the global-batch form over a process group is ``parallel.dist_info_nce_loss``.
     """
+    fused = _check_backward(backward, "info_nce_loss")
     h = _stack_views(h, z2)
     if _use_reference(h):
         return _reference_loss(reference.info_nce_loss, h, temperature)
@@ -76,7 +97,7 @@ def info_nce_loss(h: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tenso
     if comp == "fp8":
         comp = "fp16"
     tau = temperature if temperature_wants_grad(temperature) else None
-    return InfoNCEFunction.apply(h, temperature_value(temperature), comp, tau)
+    return InfoNCEFunction.apply(h, temperature_value(temperature), comp, tau, fused)
 
 
 class InfoNCELoss(_CrossViewModule):
@@ -90,15 +111,18 @@ class InfoNCELoss(_CrossViewModule):
     """
 
     def __init__(self, temperature: float = 0.07, compute: str = "auto", use_mixed_precision: bool = False,
-                 learnable_temperature: bool = False, temperature_bounds=(0.01, 1.0)):
+                 learnable_temperature: bool = False, temperature_bounds=(0.01, 1.0), backward: str = "stored"):
         super().__init__()
+        _check_backward(backward, "InfoNCELoss")
+        self.backward_mode = backward
         self.compute = compute
         self.use_mixed_precision = use_mixed_precision
         self._init_temperature(temperature, learnable_temperature, temperature_bounds)
 
     def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
         return info_nce_loss(z1, self.current_temperature(), z2=z2, compute=self.compute,
-                             use_mixed_precision=self.use_mixed_precision)
+                             use_mixed_precision=self.use_mixed_precision, backward=self.backward_mode)
 
     def extra_repr(self) -> str:
-        return f"temperature={self.temperature}, compute={self.compute}" + self._temperature_repr()
+        mode = f", backward={self.backward_mode}" if self.backward_mode != "stored" else ""
+        return f"temperature={self.temperature}, compute={self.compute}" + mode + self._temperature_repr()

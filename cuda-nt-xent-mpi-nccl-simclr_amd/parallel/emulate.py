@@ -69,12 +69,16 @@ def emulated_dist_forward_backward(shards: Sequence[torch.Tensor], temperature: 
 
 
 def emulated_xview_forward_backward(shards: Sequence[torch.Tensor], temperature: float, *, compute: str = "auto",
-                                    grad_out: float = 1.0) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+                                    grad_out: float = 1.0,
+                                    backward: str = "stored") -> Tuple[torch.Tensor, List[torch.Tensor]]:
     """Distributed cross-view InfoNCE (:mod:`parallel.infonce`) for W virtual ranks on one device:
     loss of the global batch in pair order and per-rank dL/dh_r for shards h_r = [a_r; b_r]. Every
-    rank's prep writes its slot of the shared ``zq_all`` and its merge its slot of ``lse2_all``."""
+    rank's prep writes its slot of the shared ``zq_all`` and its merge its slot of ``lse2_all``.
+    ``backward``: ``"stored"`` or ``"fused"``, as ``dist_info_nce_loss``."""
+    from ..ops.infonce import _check_backward
     from .infonce import _CDT, xview_compute, xview_stage_forward
 
+    fused = _check_backward(backward, "emulated_xview_forward_backward")
     C = _ext.load()
     W = len(shards)
     R, d = shards[0].shape
@@ -93,7 +97,8 @@ def emulated_xview_forward_backward(shards: Sequence[torch.Tensor], temperature:
         loss = loss + share  # "all-reduce" (fp64 shares)
         cposs.append(cpos)
     go = torch.tensor([grad_out], dtype=torch.float32, device=dev)
-    return loss.float(), [C.xview_dist_backward(hs[r], zq_all, preps[r][1], lse2_all, cposs[r], go, plans[r]) for r in range(W)]
+    return loss.float(), [C.xview_dist_backward(hs[r], zq_all, preps[r][1], lse2_all, cposs[r], go, plans[r], fused=fused)
+                          for r in range(W)]
 
 
 def emulated_sigmoid_forward_backward(shards: Sequence[torch.Tensor], temperature: float, bias: float, *,

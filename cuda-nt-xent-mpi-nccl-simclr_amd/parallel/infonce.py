@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _ext, reference
-from ..ops.infonce import info_nce_loss
+from ..ops.infonce import _check_backward, info_nce_loss
 from ..ops.ntxent import _stack_views, refuse_temperature_grad, resolve_compute, temperature_value
 from .commstats import span
 from .distributed import _all_gather_into, _world
@@ -80,8 +80,9 @@ def _gather_prologue(C, h: torch.Tensor, temperature: float, compute: str, group
 
 class DistInfoNCEFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h: torch.Tensor, temperature: float, compute: str, group, overlap: bool):
+    def forward(ctx, h: torch.Tensor, temperature: float, compute: str, group, overlap: bool, fused: bool = False):
         C = _ext.load()
+        ctx.fused = fused
         h = h.contiguous()
         plan, zq_all, (_, inv, ypos, _), wait = _gather_prologue(C, h, temperature, compute, group, overlap)
         W, r, Rpad = plan.world, plan.rank, plan.rows_pad
@@ -99,38 +100,45 @@ class DistInfoNCEFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out: torch.Tensor):
         h, zq_all, inv, lse2_all, cpos = ctx.saved_tensors
-        dh = _ext.load().xview_dist_backward(h, zq_all, inv, lse2_all, cpos, grad_out.reshape(1), ctx.plan)
-        return dh, None, None, None, None
+        dh = _ext.load().xview_dist_backward(h, zq_all, inv, lse2_all, cpos, grad_out.reshape(1), ctx.plan,
+                                             fused=ctx.fused)
+        return dh, None, None, None, None, None
 
 
 def dist_info_nce_loss(h_local: torch.Tensor, temperature=0.07, *, z2: Optional[torch.Tensor] = None, group=None,
-                       compute: str = "auto", use_mixed_precision: bool = False, overlap: bool = True) -> torch.Tensor:
+                       compute: str = "auto", use_mixed_precision: bool = False, overlap: bool = True,
+                       backward: str = "stored") -> torch.Tensor:
     """Global cross-view InfoNCE over the data-parallel group; ``h_local = [a_r; b_r]`` on each rank
     (or ``h_local = a_r, z2 = b_r``), the same n and d on every rank.
 
     compute: ``auto|fp32|fp16|bf16|fp8`` as for ``info_nce_loss`` (``fp8`` computes in fp16).
     overlap: launch the tiles of the own column block before the row gather is waited for (the same
-    bits either way). A temperature that requires grad is refused, as in every distributed path.
+    bits either way). backward: ``"stored"`` or ``"fused"`` as for ``info_nce_loss``: the fused backward
+    holds no n x N coefficient block (4 n_pad W n_pad bytes per rank). A temperature that requires grad is refused, as in every distributed path.
     Without a process group, or in a group of one, this is ``info_nce_loss``. CPU tensors take
     ``cpu_dist_info_nce_loss``.
     """
+    fused = _check_backward(backward, "dist_info_nce_loss")
     refuse_temperature_grad(temperature, "dist_info_nce_loss")
     W, _ = _world(group)
     if W == 1:
-        return info_nce_loss(h_local, temperature, z2=z2, compute=compute, use_mixed_precision=use_mixed_precision)
+        return info_nce_loss(h_local, temperature, z2=z2, compute=compute, use_mixed_precision=use_mixed_precision,
+                             backward=backward)
     h = _stack_views(h_local, z2)
     if not h.is_cuda:
         return cpu_dist_info_nce_loss(h, temperature, group=group)
     comp = xview_compute(h.dtype, use_mixed_precision, compute)
-    return DistInfoNCEFunction.apply(h, temperature_value(temperature), comp, group, bool(overlap))
+    return DistInfoNCEFunction.apply(h, temperature_value(temperature), comp, group, bool(overlap), fused)
 
 
 class DistInfoNCELoss(torch.nn.Module):
     """``nn.Module`` front end: ``DistInfoNCELoss(temperature)(z1, z2)`` or ``(h)`` on every rank."""
 
     def __init__(self, temperature=0.07, compute: str = "auto", group=None, use_mixed_precision: bool = False,
-                 overlap: bool = True):
+                 overlap: bool = True, backward: str = "stored"):
         super().__init__()
+        _check_backward(backward, "DistInfoNCELoss")
+        self.backward_mode = backward
         self.temperature = temperature
         self.compute = compute
         self.group = group
@@ -139,10 +147,12 @@ class DistInfoNCELoss(torch.nn.Module):
 
     def forward(self, z1: torch.Tensor, z2: Optional[torch.Tensor] = None) -> torch.Tensor:
         return dist_info_nce_loss(z1, self.temperature, z2=z2, group=self.group, compute=self.compute,
-                                  use_mixed_precision=self.use_mixed_precision, overlap=self.overlap)
+                                  use_mixed_precision=self.use_mixed_precision, overlap=self.overlap,
+                                  backward=self.backward_mode)
 
     def extra_repr(self) -> str:
-        return f"temperature={temperature_value(self.temperature)}, compute={self.compute}"
+        mode = f", backward={self.backward_mode}" if self.backward_mode != "stored" else ""
+        return f"temperature={temperature_value(self.temperature)}, compute={self.compute}" + mode
 
 
 # ---------------------------------------------------------------------------------------

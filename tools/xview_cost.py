@@ -23,6 +23,11 @@ times one virtual rank of the distributed form (``ntxent_amd.parallel.dist_info_
 its forward + backward stage ops against gathered buffers filled on the device (no collective is
 timed), B = 4096 per view and rank, against the eager PyTorch expression of the same per-rank work,
 with the per-rank peak memory of both beside the gathered buffers (``world_cost``).
+
+  python tools/xview_cost.py --backward fused [--world W]
+
+adds the arm ``op_fused``, the same op with ``backward="fused"`` (no stored coefficient block), to the
+alternating rounds, and records its backward time, its peak bytes and the ratio fused / stored.
 """
 from __future__ import annotations
 
@@ -73,6 +78,16 @@ def peak_delta(fn) -> int:
     fn()
     torch.cuda.synchronize()
     return torch.cuda.max_memory_allocated() - base
+
+
+def fused_record(rec, mem):
+    """With the arm ``op_fused``: its backward time, peak bytes and time against the stored backward."""
+    if "op_fused" in rec:
+        rec.update(op_fused_backward_median_ms=rec["op_fused"]["median_ms"] - rec["op_forward"]["median_ms"],
+                   fused_over_stored=rec["op_fused"]["median_ms"] / rec["op"]["median_ms"],
+                   peak_bytes_op_fused=mem["op_fused"])
+        print(f"  backward=fused: op {rec['op_fused']['median_ms']:.4f} ms (stored {rec['op']['median_ms']:.4f}), peak MiB "
+              f"{mem['op_fused'] / 2**20:.1f} (stored {mem['op'] / 2**20:.1f})", flush=True)
 
 
 def world_cost(args, dev):
@@ -130,7 +145,13 @@ def world_cost(args, dev):
             loss.backward()
             return loss
 
+        def op_fused():
+            inv, cpos, _ = op_forward()
+            return C.xview_dist_backward(h, zq_all, inv, lse2_all, cpos, go, plan, fused=True)
+
         arms = {"op": op, "eager": eager, "op_forward": op_forward}
+        if args.backward == "fused":
+            arms["op_fused"] = op_fused
         for fn in arms.values():
             for _ in range(args.warmup):
                 fn()
@@ -140,8 +161,9 @@ def world_cost(args, dev):
             for k, fn in arms.items():
                 ms[k] += time_arm(fn, args.iters)
         x.grad = None
-        mem = {k: peak_delta(arms[k]) for k in ("op", "eager")}
+        mem = {k: peak_delta(arms[k]) for k in arms if k != "op_forward"}
         rec = {k: summary(v) for k, v in ms.items()}
+        fused_record(rec, mem)
         rec.update(batch=batch, dim=dim, rows=2 * batch, world=W,
                    op_over_eager=rec["op"]["median_ms"] / rec["eager"]["median_ms"],
                    op_backward_median_ms=rec["op"]["median_ms"] - rec["op_forward"]["median_ms"],
@@ -166,6 +188,8 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--world", type=int, default=1,
                     help="W > 1: one virtual rank of the distributed form against device-filled gathered buffers")
+    ap.add_argument("--backward", choices=("stored", "fused"), default="stored",
+                    help="fused: also time the op with backward='fused', in the same alternating rounds")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("xview_cost: needs a GPU (no CPU fall-back: a CPU time says nothing here)")
@@ -206,6 +230,8 @@ def main(argv=None):
             "ntxent": fwd_bwd(lambda t: ntxent_amd.ntxent_loss(t, TAU)),
             "op_forward": op_forward,
         }
+        if args.backward == "fused":
+            arms["op_fused"] = fwd_bwd(lambda t: ntxent_amd.info_nce_loss(t, TAU, backward="fused"))
         for fn in arms.values():
             for _ in range(args.warmup):
                 fn()
@@ -215,10 +241,11 @@ def main(argv=None):
             for k, fn in arms.items():
                 ms[k] += time_arm(fn, args.iters)
         x.grad = None
-        mem = {k: peak_delta(arms[k]) for k in ("op", "eager")}
+        mem = {k: peak_delta(arms[k]) for k in arms if k not in ("op_forward", "ntxent")}
         with torch.no_grad():
             l_op, l_eager = float(ntxent_amd.info_nce_loss(h, TAU)), float(eager_clip(h))
         rec = {k: summary(v) for k, v in ms.items()}
+        fused_record(rec, mem)
         rec.update(batch=batch, dim=dim, rows=2 * batch,
                    op_over_eager=rec["op"]["median_ms"] / rec["eager"]["median_ms"],
                    op_over_ntxent=rec["op"]["median_ms"] / rec["ntxent"]["median_ms"],
