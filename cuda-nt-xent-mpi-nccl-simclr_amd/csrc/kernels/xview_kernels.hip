@@ -24,16 +24,18 @@
 //                       stable when P_ip -> 1) into this rank's slot of lse2; the loss terms are
 //                       formed in fp64 relative to y_pos.
 //   xview_loss_kernel : their sum in a fixed order (one block, fp64 tree). No atomics anywhere.
-//   xview_side_coef_kernel : the same tile GEMM again for ONE side; the epilogue forms the tile of G
-//                       from the gathered lse2 and cpos and stores it once, row-major [n_pad][W n_pad]
-//                       planes in the compute dtype (zeros outside the valid rows and columns): one
-//                       fp32 plane, or for 16-bit plans G rounded to the dtype and the scaled residual
-//                       of that rounding, so that the MFMA operands carry the coefficients to about
-//                       twice the dtype's mantissa (a gradient of equal coefficients is otherwise off
-//                       by the dtype's rounding of that one number). The only n N data, 4 n_pad W n_pad
-//                       bytes in every plan, and only of the stored backward: xview_fused_bwd_kernel
-//                       (below, after xview_dz_kernel) forms the same tiles of G and never stores them. Side 1 swaps the operand roles and so gives the rows of
-//                       G^T directly.
+//   xview_side_coef_kernel : the same tile GEMM again for ONE side; the loss's G step (a functor in
+//                       the kernel's parameters: XvInfoNceG forms the tile of G from the gathered
+//                       lse2 and cpos) emits the tile, which is stored once, row-major
+//                       [n_pad][W n_pad] planes in the compute dtype (zeros outside the valid rows
+//                       and columns): one fp32 plane, or for 16-bit plans G rounded to the dtype and
+//                       the scaled residual of that rounding, so that the MFMA operands carry the
+//                       coefficients to about twice the dtype's mantissa (a gradient of equal
+//                       coefficients is otherwise off by the dtype's rounding of that one number).
+//                       The only n N data, 4 n_pad W n_pad bytes in every plan, and only of the
+//                       stored backward: xview_fused_bwd_kernel (below, after xview_dz_kernel) calls
+//                       the same G step and never stores its tiles. Side 1 swaps the operand roles
+//                       and so gives the rows of G^T directly.
 //   xview_transpose_kernel : Zt[v][e][q n_pad + c] = zq[q rows_pad + v n + c][e] for every slot q,
 //                       both views aligned at column 0 of their slot and zero padded to n_pad columns
 //                       and roundup(dim_k, 128) rows (view 2 starts at row n, usually not tile aligned).
@@ -53,13 +55,19 @@
 //   - the backward stores G once (side 0) and xview_gt_kernel transposes the planes in place between
 //     the two dZ products, instead of a second coefficient pass.
 //
-// The pairwise sigmoid loss (the SigLIP form) is two more epilogues of the same tile GEMM,
-// xview_sigmoid_fwd_kernel and xview_sigmoid_coef_kernel (below, beside the family): no LSE, no
-// column partials; its coefficient block goes through the same transposes and dZ products. 16-bit
-// plans take the positives' cosines from the fp32 unit rows (xview_sigmoid_pos_kernel). Rank r of W:
-// the forward runs side 0's n x W n block alone (every global pair is computed once, on the rank
-// that holds its row a_i), the coefficient pass one side at a time as xview_side_coef_kernel; one
-// GPU is W = 1, side 0 of both, with the in-place transpose in place of side 1.
+// The pairwise sigmoid loss (the SigLIP form) is one more forward epilogue of the same tile GEMM,
+// xview_sigmoid_fwd_kernel, and one more G step, XvSigmoidG, in xview_side_coef_kernel (below, beside
+// the family): no LSE, no column partials; its coefficient block goes through the same transposes and
+// dZ products. 16-bit plans take the positives' cosines from the fp32 unit rows
+// (xview_sigmoid_pos_kernel). Rank r of W: the forward runs side 0's n x W n block alone (every
+// global pair is computed once, on the rank that holds its row a_i), the coefficient pass one side at
+// a time; one GPU is W = 1, side 0 of both, with the in-place transpose in place of side 1.
+//
+// A loss on this family is a forward epilogue and ONE G step (see XvInfoNceG): a trivially copyable
+// functor that carries its own arguments, from which xview_side_coef_kernel gives the stored backward
+// and xview_fused_bwd_kernel the fused one, with the same coefficient bits. The kernels share the
+// lane's place in a tile (XvLane), the slot-range tile decode (xv_slot_tile), the hi / residual plane
+// split (xv_store_planes) and the slab-row store (xv_store_slab_rows).
 // The block form of both epilogues (kBlock) and of the dZ product (kAccum) serves the ring exchange:
 // this rank's one slot against one other rank's slot at a time, the same arithmetic, the partials at
 // the gather launches' places and the dZ slab accumulated block after block (the rows_q / kslots = 1
@@ -68,6 +76,8 @@
 #include "device_common.h"
 #include "host_common.h"
 #include "tile128.h"
+
+#include <type_traits>
 
 namespace ntxent {
 namespace dev {
@@ -84,24 +94,79 @@ struct XvParams {
   int nk;             // 128-byte K-steps per row of zq
   int nT;             // n_pad / 128: 128-row tiles per view of a slot
   int world, rank;
-  int q_lo, nq, q_skip;  // forward: the launch's column slots, nq of them from q_lo on, q_skip left out
-  int side;           // coefficient pass: the side
-  float scale2;       // log2(e) / tau: cosine -> logit in log2 units
+  int q_lo, nq, q_skip;  // the launch's column slots, nq of them from q_lo on, q_skip left out
+  float scale2;       // InfoNCE: log2(e) / tau: cosine -> logit in log2 units
   float2* part;       // forward: [world * nT][rows_pad] (launch_lse's layout), row side * n + l
   float* ypos;        // forward: [>= n] positive logits of the pairs (log2 units), written
-  const float* lse2;  // coefficient pass: [world * rows_pad] gathered LSE (log2 units, positive included)
-  const float* cpos;  //                   [rows_pad] positive coefficients of this rank's rows
-  char* gbuf;         // [planes][n_pad][ldg bytes] G in the compute dtype (16-bit: residual plane, hi plane)
-  long long ldg;
-  long long plane_bytes;
   // block form (kBlock kernels): zq is this rank's own ONE slot [rows_pad][ldb], zcol a one-slot buffer
   // of the same shape that holds rank q_lo's rows (the own block: zq itself). q_lo is the slot's
   // identity: it drives own = (q == rank), the positive test and the output place, no buffer index.
   const char* zcol;
 };
+
+// A lane's part of a tile in tile128.h's accumulator layout: wave (wr, wc) of the 2 x 2 waves holds a
+// 64 x 64 quarter, and acc[mi][ni][r] is the tile's element (row(mi, r), col(ni)).
+struct XvLane {
+  int wr, wc, r16, g;
+  __device__ __forceinline__ XvLane() {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  }
+  __device__ __forceinline__ int row(int mi, int r) const { return 64 * wr + 16 * mi + 4 * g + r; }
+  __device__ __forceinline__ int col(int ni) const { return 64 * wc + 16 * ni + r16; }
+};
+
+// Tile b of a launch over p's slot range: row tile I against local tile Jl of slot q, I-major, the
+// slots ascending from q_lo with q_skip left out.
+struct XvTile {
+  int I, q, Jl;
+};
+__device__ __forceinline__ XvTile xv_slot_tile(const XvParams& p, int b) {
+  const int ncol = p.nq * p.nT;
+  const int I = b / ncol, jj = b - I * ncol;
+  int q = p.q_lo + jj / p.nT;
+  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
+  return {I, q, jj % p.nT};
+}
+
 // 16-bit plans: the residual plane holds (G - hi) * kXvLoScale, clear of fp16's subnormals; the dZ
 // runs it first and scales its accumulators back (a power of two: exact) before the hi plane.
 constexpr float kXvLoScale = 2048.f;
+
+// Coefficient v into the planes in the compute dtype, at `at` of the first plane (the second `plane`
+// elements on): fp32 plans one plane, v; 16-bit plans the residual plane (v - hi) * 2^11, then hi = v
+// rounded to T. The dZ adds both, so the coefficients carry about 2 x the operand's mantissa.
+template <typename T, typename Ptr>
+__device__ __forceinline__ void xv_store_planes(Ptr at, int plane, float v) {
+  const T hi = from_f32<T>(v);
+  if constexpr (sizeof(T) == 2) {
+    at[0] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
+    at[plane] = hi;
+  } else {
+    at[0] = hi;
+  }
+}
+
+// acc's rows m0 + row below n into an fp32 slab, 128 columns from out[0] on (out: the view's first
+// row at the tile's first column). kAccum: added to what is there, with plain loads and stores.
+template <bool kAccum>
+__device__ __forceinline__ void xv_store_slab_rows(float* out, long long ldo, int m0, int n, const XvLane& ln,
+                                                   const f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = m0 + ln.row(mi, r);
+      if (m < n) {
+        float* orow = out + (long long)m * ldo + ln.col(0);
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          if constexpr (kAccum) orow[16 * ni] = orow[16 * ni] + acc[mi][ni][r];
+          else orow[16 * ni] = acc[mi][ni][r];
+        }
+      }
+    }
+}
 
 // acc = tile (I, Jl of slot q) of side `side`: rows side * n + I * 128 .. of the own slot against
 // rows (1 - side) * n + Jl * 128 .. of slot q. Ends with a block barrier: the caller's epilogue may
@@ -126,15 +191,11 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   // ONE __shared__ object (staging ring, reused by the epilogue)
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const int tid = threadIdx.x;
+  const XvLane ln;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int ncol = p.nq * p.nT, per_side = p.nT * ncol;
-  const int side = b / per_side, rem = b - side * per_side;
-  const int I = rem / ncol, jj = rem - I * ncol;
-  int q = p.q_lo + jj / p.nT;
-  const int Jl = jj % p.nT;
-  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
+  const int per_side = p.nT * p.nq * p.nT, side = b / per_side;
+  const auto [I, q, Jl] = xv_slot_tile(p, b - side * per_side);
   const int n = p.n;
   const bool own = q == p.rank;
 
@@ -151,7 +212,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   [[maybe_unused]] float cm[4], cs[4];
 #pragma unroll
   for (int ni = 0; ni < 4; ++ni) {
-    cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+    cl[ni] = Jl * kXvTile + ln.col(ni);
     if constexpr (kCols) {
       cm[ni] = kNegInf;
       cs[ni] = 0.f;
@@ -163,7 +224,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int li = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+      const int li = I * kXvTile + ln.row(mi, r);
       float m = kNegInf;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
@@ -192,7 +253,7 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int rt = 64 * wr + 16 * mi + 4 * g + r;
+      const int rt = ln.row(mi, r);
       const float mr = rmx[mi][r];
       float s = 0.f;
 #pragma unroll
@@ -203,19 +264,19 @@ __global__ __launch_bounds__(kXvThreads) void xview_fwd_kernel(const XvParams p)
         if constexpr (kCols) cs[ni] += ok ? fast_exp2(y - cm[ni]) : 0.f;
       }
       s = row16_sum(s);
-      if (r16 == 0) {
-        s_rm[wc * kXvTile + rt] = mr;
-        s_rs[wc * kXvTile + rt] = s;
+      if (ln.r16 == 0) {
+        s_rm[ln.wc * kXvTile + rt] = mr;
+        s_rs[ln.wc * kXvTile + rt] = s;
       }
     }
   if constexpr (kCols) {
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
       cs[ni] = xrow_sum(cs[ni]);
-      if (g == 0) {
-        const int ct = 64 * wc + 16 * ni + r16;
-        s_cm[wr * kXvTile + ct] = cm[ni];
-        s_cs[wr * kXvTile + ct] = cs[ni];
+      if (ln.g == 0) {
+        const int ct = ln.col(ni);
+        s_cm[ln.wr * kXvTile + ct] = cm[ni];
+        s_cs[ln.wr * kXvTile + ct] = cs[ni];
       }
     }
   }
@@ -307,92 +368,113 @@ __global__ __launch_bounds__(kXvSumThreads) void xview_loss_kernel(const double*
 }
 
 // ---- backward: the G step, from a tile of S in tile128.h's accumulator layout to the tile of G ------
+// A G step is a small trivially copyable struct that holds what only its loss needs and travels by
+// value inside the kernel's parameters. Its operator()(p, side, I, q, Jl, acc, emit) calls
+// emit(rt, ct, v) exactly once for every element (rt, ct) of the 128 x 128 tile, in the order mi, r,
+// ni of XvLane: v is the coefficient, or zero for rows and columns at or beyond n of their slot,
+// chosen by a select and never by a product (outside the valid rows and columns the arithmetic may
+// overflow). kBiasSum: the stored kernel also sums the emitted values per wave (bias_part).
+// kBlockForm: the step indexes no buffer by the slot q, so it also serves the kBlock kernels.
+// Both backwards call the same G step (the stored block's kernel and the fused kernel), so their
+// coefficients are the same bits. A new loss's stored AND fused backward is one such functor:
+// instantiate xview_side_coef_kernel and xview_fused_bwd_kernel with it and fill it on the host.
+//
 // InfoNCE's: G_ij = exp2(y_ij - lse2_i) + exp2(y_ij - lse2_j) from the own and the gathered lse2, cpos
-// on the positives of the own slot, zero for rows and columns at or beyond n of their slot. emit(rt,
-// ct, v): element (rt, ct) of the 128 x 128 tile, each once. Both backwards call this one function
-// (the stored block's kernel and the fused kernel), so their coefficients are the same bits; another
-// loss's G step is another functor of this shape.
+// on the positives of the own slot. lse2 is indexed by the slot q: the gather form only.
 struct XvInfoNceG {
+  static constexpr bool kBiasSum = false, kBlockForm = false;
+  const float* lse2;  // [world * rows_pad] gathered LSE (log2 units, positive included)
+  const float* cpos;  // [rows_pad] positive coefficients of this rank's rows
   template <class Emit>
   __device__ __forceinline__ void operator()(const XvParams& p, int side, int I, int q, int Jl,
                                              const f32x4 (&acc)[4][4], Emit emit) const {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+    const XvLane ln;
     const int n = p.n;
     const bool own = q == p.rank;
-    const float* lrow = p.lse2 + (long long)p.rank * p.rows_pad + side * n;
-    const float* lcol = p.lse2 + (long long)q * p.rows_pad + (1 - side) * n;
+    const float* lrow = lse2 + (long long)p.rank * p.rows_pad + side * n;
+    const float* lcol = lse2 + (long long)q * p.rows_pad + (1 - side) * n;
     int cl[4];
     float lc[4];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
-      cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
+      cl[ni] = Jl * kXvTile + ln.col(ni);
       lc[ni] = cl[ni] < n ? lcol[cl[ni]] : 0.f;
     }
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int rt = 64 * wr + 16 * mi + 4 * g + r;
+        const int rt = ln.row(mi, r);
         const int li = I * kXvTile + rt;
         const float lr = li < n ? lrow[li] : 0.f;
-        const float cp = li < n ? p.cpos[side * n + li] : 0.f;
+        const float cp = li < n ? cpos[side * n + li] : 0.f;
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           const float y = acc[mi][ni][r] * p.scale2;
           const bool ok = (li < n) & (cl[ni] < n);
           const float c = fast_exp2(y - lr) + fast_exp2(y - lc[ni]);
-          // selects, not products: outside the valid rows and columns the exponentials may overflow
           const float v = ok ? ((own & (cl[ni] == li)) ? cp : c) : 0.f;
-          emit(rt, 64 * wc + 16 * ni + r16, v);
+          emit(rt, ln.col(ni), v);
         }
       }
   }
 };
 
 // ---- backward: tile (I, J) of one side's n_pad x W n_pad block G, stored once ----------------------
-template <typename T>
-__global__ __launch_bounds__(kXvThreads) void xview_side_coef_kernel(const XvParams p) {
+template <class GStep>
+struct XvCoefParams {
+  XvParams x;         // the tile GEMM's operands
+  GStep g;
+  int side;
+  char* gbuf;         // [planes][n_pad][ldg bytes] G in the compute dtype (16-bit: residual plane, hi plane)
+  long long ldg;
+  long long plane_bytes;
+  float* bias_part;   // kBiasSum: [nT * world * nT][4] the waves' sums of the tile's G; null: not stored
+};
+
+// kBlock: one side of the ONE block of slot q = q_lo, nT x nT tiles of the one-slot operands, stored
+// as planes [n_pad][n_pad] (J = Jl). kBiasSum: the sums are taken from the fp32 values before they
+// are rounded to the planes; the plane image fills the whole __shared__ object, so every wave reduces
+// in its registers and stores one fp32 partial to bias_part[tile][wave], the tile's place in the
+// n_pad x W n_pad block in both forms (the gather form's b).
+template <typename T, class GStep, bool kBlock = false>
+__global__ __launch_bounds__(kXvThreads) void xview_side_coef_kernel(const XvCoefParams<GStep> pc) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
+  const XvParams& p = pc.x;
   const int tid = threadIdx.x;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
-  const int ncol = p.world * p.nT;
+  const int ncol = kBlock ? p.nT : p.world * p.nT;
   const int I = b / ncol, J = b - I * ncol;
-  const int q = J / p.nT, Jl = J - q * p.nT;
-  const int side = p.side;
+  const int q = kBlock ? p.q_lo : J / p.nT, Jl = kBlock ? J : J - q * p.nT;
 
   f32x4 acc[4][4];
-  xv_tile_gemm<T>(p, side, I, q, Jl, lds, acc);
+  xv_tile_gemm<T, kBlock>(p, pc.side, I, q, Jl, lds, acc);
 
-  // the tile's planes in the compute dtype, row-major [128][128] each, over the staging images
-  // (64 KiB): fp32 plans one plane, G; 16-bit plans the residual plane (G - hi) * 2^11, then hi =
-  // G rounded to T. The dZ adds both, so the coefficients carry about 2 x the operand's mantissa.
-  constexpr bool kSplit = sizeof(T) == 2;
-  constexpr int kPlaneElems = kXvTile * kXvTile;
+  // the tile's planes, row-major [128][128] each, over the staging images (64 KiB)
   T* s_g = reinterpret_cast<T*>(smem);
-  XvInfoNceG{}(p, side, I, q, Jl, acc, [&](int rt, int ct, float v) __attribute__((always_inline)) {
-    const int at = rt * kXvTile + ct;
-    const T hi = from_f32<T>(v);
-    if constexpr (kSplit) {
-      s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
-      s_g[kPlaneElems + at] = hi;
-    } else {
-      s_g[at] = hi;
-    }
+  [[maybe_unused]] float bsum = 0.f;
+  pc.g(p, pc.side, I, q, Jl, acc, [&](int rt, int ct, float v) __attribute__((always_inline)) {
+    if constexpr (GStep::kBiasSum) bsum += v;
+    xv_store_planes<T>(s_g + rt * kXvTile + ct, kXvTile * kXvTile, v);
   });
+  if constexpr (GStep::kBiasSum) {
+    bsum = wave_sum(bsum);
+    const int bplace = kBlock ? (I * p.world + q) * p.nT + Jl : b;
+    if (pc.bias_part && (tid & 63) == 0) pc.bias_part[bplace * 4 + (tid >> 6)] = bsum;
+  }
   __syncthreads();
   // 16-byte chunks, rows contiguous: 8 * sizeof(T) chunks per row, 4096 chunks in all
   constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
   constexpr int kCpp = kCpr * kXvTile;  // chunks per plane
-  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
+  char* gt = pc.gbuf + (long long)I * kXvTile * pc.ldg + (long long)J * kXvTile * (int)sizeof(T);
 #pragma unroll
   for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
     const int idx = c * kXvThreads + tid;
     const int plane = idx / kCpp, in = idx - plane * kCpp;
     const int row = in / kCpr, cc = in - row * kCpr;
     const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
-    *reinterpret_cast<u32x4*>(gt + plane * p.plane_bytes + (long long)row * p.ldg + cc * 16) = v;
+    *reinterpret_cast<u32x4*>(gt + plane * pc.plane_bytes + (long long)row * pc.ldg + cc * 16) = v;
   }
 }
 
@@ -469,8 +551,6 @@ template <typename T, bool kAccum = false>
 __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p) {
   __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
   lds_char* lds = (lds_char*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
   const int Ei = blockIdx.x, Mi = blockIdx.y, side = p.side;
 
   // A: rows Mi * 128 .. of the coefficient planes; B: rows e of the OTHER view's Zt; K along both
@@ -499,21 +579,8 @@ __global__ __launch_bounds__(kXvThreads) void xview_dz_kernel(const XvDzParams p
       acc);
 
   // rows of this view at or beyond N do not exist (the coefficients are zero there anyway)
-  float* out = p.out;
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = Mi * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
-      if (m < p.n_half) {
-        float* orow = out + ((long long)side * p.n_half + m) * p.ldo + (long long)Ei * kXvTile + 64 * wc + r16;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-          if constexpr (kAccum) orow[16 * ni] = orow[16 * ni] + acc[mi][ni][r];
-          else orow[16 * ni] = acc[mi][ni][r];
-        }
-      }
-    }
+  xv_store_slab_rows<kAccum>(p.out + (long long)side * p.n_half * p.ldo + (long long)Ei * kXvTile, p.ldo, Mi * kXvTile,
+                             p.n_half, XvLane(), acc);
 }
 
 // ---- fused backward: out = G Z without G in memory ---------------------------------------------------
@@ -547,8 +614,10 @@ constexpr int kXvFuseSubs = kXvFuseChunk / kXvTile;
 constexpr int kXvFuseLds = 2 * kTile128Lds;  // the staging ring, then the G images
 constexpr int kXvFuseMaxSplits = 4;
 
+template <class GStep>
 struct XvFuseParams {
-  XvParams x;        // the tile GEMM's operands, lse2 and cpos (side: blockIdx.y)
+  XvParams x;        // the tile GEMM's operands (side: blockIdx.y)
+  GStep g;
   const char* zt;    // [2][En][ldz bytes]
   long long ldz;
   int En;            // roundup(dim_k, 128)
@@ -560,15 +629,14 @@ struct XvFuseParams {
 };
 
 template <typename T, class GStep>
-__global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFuseParams pf) {
+__global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFuseParams<GStep> pf) {
   // ONE __shared__ object
   __shared__ __attribute__((aligned(16))) char smem[kXvFuseLds];
   typedef __attribute__((address_space(3))) T lds_T;
   lds_char* ring = (lds_char*)smem;
   lds_char* gimg = ring + kTile128Lds;
   const XvParams& p = pf.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
+  const XvLane ln;
   const int side = blockIdx.y;
   const int b = xcd_remap(blockIdx.x, gridDim.x);
   const int s = b % pf.kc, be = b / pf.kc;
@@ -595,16 +663,10 @@ __global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFus
     {
       f32x4 acc[4][4];
       xv_tile_gemm<T>(p, side, I, q, Jl, ring, acc);  // ends with a barrier: the last tile's images are free
-      GStep{}(p, side, I, q, Jl, acc, [&](int rt, int ct, float v) __attribute__((always_inline)) {
+      pf.g(p, side, I, q, Jl, acc, [&](int rt, int ct, float v) __attribute__((always_inline)) {
         const int kb = ct * (int)sizeof(T);  // byte along K
         lds_char* at = gimg + (kb >> 7) * kTile128Stage + tile128_off(rt, (kb & 127) >> 4) + (kb & 15);
-        const T hi = from_f32<T>(v);
-        if constexpr (kSplit) {
-          *(lds_T*)at = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
-          *(lds_T*)(at + kKs * kTile128Stage) = hi;
-        } else {
-          *(lds_T*)at = hi;
-        }
+        xv_store_planes<T>((lds_T*)at, kKs * kTile128Stage / (int)sizeof(T), v);
       });
     }
     // steps t = sub * kKs + k: the tile's K-steps for one e sub-tile after the other
@@ -624,8 +686,8 @@ __global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFus
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) lo[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
-            tile128_mma_step<T>(gimg + k * kTile128Stage, bimg, wr, wc, r16, g, lo);
-            tile128_mma_step<T>(gimg + (kKs + k) * kTile128Stage, bimg, wr, wc, r16, g, out[sub]);
+            tile128_mma_step<T>(gimg + k * kTile128Stage, bimg, ln.wr, ln.wc, ln.r16, ln.g, lo);
+            tile128_mma_step<T>(gimg + (kKs + k) * kTile128Stage, bimg, ln.wr, ln.wc, ln.r16, ln.g, out[sub]);
             if (k == kKs - 1) {  // the residual plane of this tile is done: back to G's scale
 #pragma unroll
               for (int mi = 0; mi < 4; ++mi)
@@ -633,30 +695,16 @@ __global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFus
                 for (int ni = 0; ni < 4; ++ni) out[sub][mi][ni] += lo[mi][ni] * (1.0f / kXvLoScale);
             }
           } else {
-            tile128_mma_step<T>(gimg + k * kTile128Stage, bimg, wr, wc, r16, g, out[sub]);
+            tile128_mma_step<T>(gimg + k * kTile128Stage, bimg, ln.wr, ln.wc, ln.r16, ln.g, out[sub]);
           }
         });
   }
 
   // rows of this view at or beyond n do not exist (the coefficients are zero there anyway)
-  float* slab = pf.dz + (long long)s * pf.slab;
+  float* slab = pf.dz + (long long)s * pf.slab + (long long)side * p.n * pf.ldo + (long long)ec * kXvFuseChunk;
 #pragma unroll
-  for (int sub = 0; sub < kXvFuseSubs; ++sub) {
-    if (sub < nsub) {
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
-          if (m < p.n) {
-            float* orow = slab + ((long long)side * p.n + m) * pf.ldo + (long long)ec * kXvFuseChunk + sub * kXvTile +
-                          64 * wc + r16;
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) orow[16 * ni] = out[sub][mi][ni][r];
-          }
-        }
-    }
-  }
+  for (int sub = 0; sub < kXvFuseSubs; ++sub)
+    if (sub < nsub) xv_store_slab_rows<false>(slab + sub * kXvTile, pf.ldo, I * kXvTile, p.n, ln, out[sub]);
 }
 
 // ---- pairwise sigmoid loss (the SigLIP form) ---------------------------------------------------------
@@ -668,22 +716,6 @@ __global__ __launch_bounds__(kXvThreads) void xview_fused_bwd_kernel(const XvFus
 // factor (a power of two: exact) makes launch_norm_bwd's grad_out / (R tau) the loss's 1 / (n tau) and
 // launch_tau_grad's -(1 / (2 R tau^2)) sum_i dot_i over both views' rows dL/dtau, so the dZ products,
 // the normalisation backward and the temperature gradient serve as they are.
-struct XvSigParams {
-  XvParams x;        // the tile GEMM's operands; the coefficient pass: gbuf / ldg / plane_bytes as well
-  // x_ij in log2 units = cos_ij * scale2 + bias2, formed in fp64 and rounded to fp32 once per pair: an
-  // fp32 scale and bias would be off by their own rounding in the same direction for every pair, which
-  // no sum over the pairs averages out (the bias gradient's sum least of all)
-  double scale2;     // log2(e) / tau
-  double bias2;      // log2(e) * bias
-  double* lpart;    // forward: [nT][world * nT] the tiles' sums of softplus terms, tile (I, q, Jl) at its place
-  float* bias_part;  // coefficient pass: [nT * world * nT][4] the waves' sums of C = 2 G; null (side 1): not stored
-  // 16-bit plans: [n] the pairs' cosines a_i . b_i from the input rows in fp32
-  // (xview_sigmoid_pos_kernel), taken for the diagonal in place of the tile's sum; null: the tile's.
-  // The N positives carry the loss, dL/dbias and dL/dtau once bias pushes the negatives down, every
-  // x_ii enters with weight 1 / N, and the mean shift of cos_ii from rounding the unit rows to 16 bits
-  // (2.6e-5 in bf16) goes through undiminished: no normaliser cancels it as a softmax loss's does.
-  const float* pos_cos;
-};
 
 // cos[i] = z_i . z_{i + n} of the fp32 unit rows z = h * inv, the operands an fp32 plan has (so rows
 // that are exact there, one-hot ones, are exact here): one wave per pair, the products summed in fp64
@@ -704,22 +736,80 @@ __global__ __launch_bounds__(256) void xview_sigmoid_pos_kernel(const Tin* __res
   if (lane == 0) cos[i] = (float)s;
 }
 
-// The pairs' cosines of the rows of a diagonal tile this lane holds (pos_cos given), else zeros.
-__device__ __forceinline__ void xv_sig_load_pos(const XvSigParams& ps, bool diag, int row0, int g, float (&pc)[4][4]) {
+// The sigmoid loss's G step (see XvInfoNceG), C = 2 G: 2 sigmoid(x) = 2 / (1 + e^-x) off the diagonal
+// and, formed directly, -2 sigmoid(-x) = -2 / (1 + e^x) on it (an overflowing exponential gives the
+// exact limit 0). Side 1 is rows b_r against a of every slot; x is symmetric in that swap, so those
+// are the rows of C^T. Nothing here indexes a buffer by the slot q: it serves the block form too.
+// kBiasSum: the tiles' sums of C are the bias gradient's partials (side 0 only: each pair counts once).
+struct XvSigmoidG {
+  static constexpr bool kBiasSum = true, kBlockForm = true;
+  // x_ij in log2 units = cos_ij * scale2 + bias2, formed in fp64 and rounded to fp32 once per pair: an
+  // fp32 scale and bias would be off by their own rounding in the same direction for every pair, which
+  // no sum over the pairs averages out (the bias gradient's sum least of all)
+  double scale2;  // log2(e) / tau
+  double bias2;   // log2(e) * bias
+  // 16-bit plans: [n] the pairs' cosines a_i . b_i from the input rows in fp32
+  // (xview_sigmoid_pos_kernel), taken for the diagonal in place of the tile's sum; null: the tile's.
+  // The N positives carry the loss, dL/dbias and dL/dtau once bias pushes the negatives down, every
+  // x_ii enters with weight 1 / N, and the mean shift of cos_ii from rounding the unit rows to 16 bits
+  // (2.6e-5 in bf16) goes through undiminished: no normaliser cancels it as a softmax loss's does.
+  const float* pos_cos;
+
+  // The pairs' cosines of the rows of a diagonal tile this lane holds (pos_cos given), else zeros.
+  __device__ __forceinline__ void load_pos(int n, bool diag, int I, const XvLane& ln, float (&pc)[4][4]) const {
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
+    for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pc[mi][r] = 0.f;
-  if (diag && ps.pos_cos) {  // block-uniform
+      for (int r = 0; r < 4; ++r) pc[mi][r] = 0.f;
+    if (diag && pos_cos) {  // block-uniform
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int li = I * kXvTile + ln.row(mi, r);
+          if (li < n) pc[mi][r] = pos_cos[li];
+        }
+    }
+  }
+  // x of one pair, log2 units: from the tile's sum s, or (a positive, pos_cos given) from pc
+  __device__ __forceinline__ double logit2(bool pos, float pc, float s) const {
+    return fma((double)((pos & (pos_cos != nullptr)) ? pc : s), scale2, bias2);
+  }
+
+  template <class Emit>
+  __device__ __forceinline__ void operator()(const XvParams& p, int /*side*/, int I, int q, int Jl,
+                                             const f32x4 (&acc)[4][4], Emit emit) const {
+    const XvLane ln;
+    const int n = p.n;
+    const bool own = q == p.rank;
+    int cl[4];
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + ln.col(ni);
+    float pc[4][4];
+    load_pos(n, own && Jl == I, I, ln, pc);
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int li = row0 + 16 * mi + 4 * g + r;
-        if (li < ps.x.n) pc[mi][r] = ps.pos_cos[li];
+        const int rt = ln.row(mi, r);
+        const int li = I * kXvTile + rt;
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+          const bool ok = (li < n) & (cl[ni] < n);
+          const bool pos = own & (cl[ni] == li);  // only in a diagonal tile (Jl == I) of the own slot
+          const float x2 = (float)logit2(pos, pc[mi][r], acc[mi][ni][r]);
+          const float c = (pos ? -2.f : 2.f) / (1.f + fast_exp2(pos ? x2 : -x2));
+          emit(rt, ln.col(ni), ok ? c : 0.f);
+        }
       }
   }
-}
+};
+
+struct XvSigParams {
+  XvParams x;     // the tile GEMM's operands and the launch's slots
+  XvSigmoidG g;   // the logit
+  double* lpart;  // [nT][world * nT] the tiles' sums of softplus terms, tile (I, q, Jl) at its place
+};
 
 // Forward: tile (I, Jl)'s sum of softplus terms, natural-log units. softplus(t) = max(t, 0) +
 // log1p(e^-|t|): the log1p form keeps a negative's term (e^-20 at cos = -1, tau = 0.1, bias = -10)
@@ -735,14 +825,9 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
   lds_char* lds = (lds_char*)smem;
   const XvParams& p = ps.x;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
+  const XvLane ln;
   // side 0's tiles (I, slot q, Jl) of the launch's slots, as xview_fwd_kernel walks a side's
-  const int ncol = p.nq * p.nT;
-  const int I = b / ncol, jj = b - I * ncol;
-  int q = p.q_lo + jj / p.nT;
-  const int Jl = jj % p.nT;
-  if (p.q_skip >= 0 && q >= p.q_skip) ++q;
+  const auto [I, q, Jl] = xv_slot_tile(p, xcd_remap(blockIdx.x, gridDim.x));
   const int n = p.n;
   const bool own = q == p.rank;
 
@@ -751,21 +836,20 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
 
   int cl[4];
 #pragma unroll
-  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
-  const bool fine_pos = ps.pos_cos != nullptr;
+  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + ln.col(ni);
   float pc[4][4];
-  xv_sig_load_pos(ps, own && Jl == I, I * kXvTile + 64 * wr, g, pc);
+  ps.g.load_pos(n, own && Jl == I, I, ln, pc);
   double sum = 0.0;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int li = I * kXvTile + 64 * wr + 16 * mi + 4 * g + r;
+      const int li = I * kXvTile + ln.row(mi, r);
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const bool in = (li < n) & (cl[ni] < n);
         const bool pos = own & (cl[ni] == li);  // only in a diagonal tile (Jl == I) of the own slot
-        const double x2 = fma((double)((pos & fine_pos) ? pc[mi][r] : acc[mi][ni][r]), ps.scale2, ps.bias2);
+        const double x2 = ps.g.logit2(pos, pc[mi][r], acc[mi][ni][r]);  // in double for the softplus
         const double t2 = pos ? -x2 : x2;  // -s_ij x_ij
         const double sp = fmax(t2, 0.0) * 0.6931471805599453 + (double)log1pf(fast_exp2(-fabsf((float)t2)));
         sum += in ? sp : 0.0;
@@ -779,89 +863,6 @@ __global__ __launch_bounds__(kXvThreads) void xview_sigmoid_fwd_kernel(const XvS
   __syncthreads();
   // the tile's own place, whichever launch runs it: the sum's order does not depend on the split
   if (tid == 0) ps.lpart[((long long)I * p.world + q) * p.nT + Jl] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
-// Coefficient pass: tile (I, J) of side p.side's n_pad x W n_pad block (side 1: rows b_r against a of
-// every slot; x is symmetric in that swap, so these are the rows of C^T), stored as
-// xview_side_coef_kernel stores G (one fp32 plane, or the
-// residual plane scaled by kXvLoScale and the hi plane; exact zeros outside the valid rows and
-// columns), with C = 2 G: 2 sigmoid(x) = 2 / (1 + e^-x) off the diagonal and, formed directly,
-// -2 sigmoid(-x) = -2 / (1 + e^x) on it (an overflowing exponential gives the exact limit 0). The bias
-// gradient's partials are taken from the fp32 values before they are rounded to the planes: the plane
-// image fills the whole __shared__ object, so every wave reduces in its registers and stores one
-// fp32 partial to bias_part[tile][wave].
-// kBlock: one side of the ONE block of slot q = q_lo, nT x nT tiles of the one-slot operands, stored as
-// planes [n_pad][n_pad] (J = Jl); the bias partials go to the tile's place in the n_pad x W n_pad
-// block, ((I W + q) nT + Jl) * 4 + wave, which is what b * 4 + w is below.
-template <typename T, bool kBlock = false>
-__global__ __launch_bounds__(kXvThreads) void xview_sigmoid_coef_kernel(const XvSigParams ps) {
-  __shared__ __attribute__((aligned(16))) char smem[kTile128Lds];
-  lds_char* lds = (lds_char*)smem;
-  const XvParams& p = ps.x;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w >> 1, wc = w & 1, r16 = lane & 15, g = lane >> 4;
-  const int b = xcd_remap(blockIdx.x, gridDim.x);
-  // tile (I, J) of one side's n_pad x W n_pad block, as xview_side_coef_kernel
-  const int ncol = kBlock ? p.nT : p.world * p.nT;
-  const int I = b / ncol, J = b - I * ncol;
-  const int q = kBlock ? p.q_lo : J / p.nT, Jl = kBlock ? J : J - q * p.nT;
-  const int n = p.n;
-  const bool own = q == p.rank;
-  const int bplace = kBlock ? (I * p.world + q) * p.nT + Jl : b;
-
-  f32x4 acc[4][4];
-  xv_tile_gemm<T, kBlock>(p, p.side, I, q, Jl, lds, acc);
-
-  constexpr bool kSplit = sizeof(T) == 2;
-  constexpr int kPlaneElems = kXvTile * kXvTile;
-  T* s_g = reinterpret_cast<T*>(smem);
-  int cl[4];
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) cl[ni] = Jl * kXvTile + 64 * wc + 16 * ni + r16;
-  const bool fine_pos = ps.pos_cos != nullptr;
-  float pc[4][4];
-  xv_sig_load_pos(ps, own && Jl == I, I * kXvTile + 64 * wr, g, pc);
-  float bsum = 0.f;
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rt = 64 * wr + 16 * mi + 4 * g + r;
-      const int li = I * kXvTile + rt;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const bool ok = (li < n) & (cl[ni] < n);
-        const bool pos = own & (cl[ni] == li);
-        const float x2 = (float)fma((double)((pos & fine_pos) ? pc[mi][r] : acc[mi][ni][r]), ps.scale2, ps.bias2);
-        const float c = (pos ? -2.f : 2.f) / (1.f + fast_exp2(pos ? x2 : -x2));
-        // a select, not a product: zeros outside the valid rows and columns
-        const float v = ok ? c : 0.f;
-        bsum += v;
-        const int at = rt * kXvTile + 64 * wc + 16 * ni + r16;
-        const T hi = from_f32<T>(v);
-        if constexpr (kSplit) {
-          s_g[at] = from_f32<T>((v - to_f32<T>(hi)) * kXvLoScale);
-          s_g[kPlaneElems + at] = hi;
-        } else {
-          s_g[at] = hi;
-        }
-      }
-    }
-  bsum = wave_sum(bsum);
-  if (ps.bias_part && lane == 0) ps.bias_part[bplace * 4 + w] = bsum;  // side 0 only: each pair counts once
-  __syncthreads();
-  // 16-byte chunks, rows contiguous, as xview_side_coef_kernel
-  constexpr int kCpr = kXvTile * (int)sizeof(T) / 16;
-  constexpr int kCpp = kCpr * kXvTile;
-  char* gt = p.gbuf + (long long)I * kXvTile * p.ldg + (long long)J * kXvTile * (int)sizeof(T);
-#pragma unroll
-  for (int c = 0; c < kTile128Lds / 16 / kXvThreads; ++c) {
-    const int idx = c * kXvThreads + tid;
-    const int plane = idx / kCpp, in = idx - plane * kCpp;
-    const int row = in / kCpr, cc = in - row * kCpr;
-    const u32x4 v = *reinterpret_cast<const u32x4*>(smem + idx * 16);
-    *reinterpret_cast<u32x4*>(gt + plane * p.plane_bytes + (long long)row * p.ldg + cc * 16) = v;
-  }
 }
 
 // dbias[0] = grad_out[0] * (sum of the `count` partials of C = 2 G) / (2 n). One block: thread t sums
@@ -962,22 +963,34 @@ void xv_launch_zt(DType comp, const void* rows, const Geometry& g, int kslots, v
   });
 }
 
-// One side's coefficient block in coef: planes of n_pad rows, kslots * n_pad columns.
-void xv_coef_planes(DType comp, const Geometry& g, int kslots, void* coef, dev::XvParams& p) {
-  p.gbuf = static_cast<char*>(coef);
-  p.ldg = (long long)kslots * xv_npad(g) * (long long)dtype_size(comp);
-  p.plane_bytes = (long long)xv_npad(g) * p.ldg;
+// f(std::true_type{} | std::false_type{}): a run-time flag as a template argument.
+template <class F>
+void dispatch_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
 }
 
-void xv_launch_coef(DType comp, dev::XvParams p, const Geometry& g, int side, const float* lse2_all,
-                    const float* cpos, void* coef, hipStream_t stream) {
-  p.side = side;
-  p.lse2 = lse2_all;
-  p.cpos = cpos;
-  xv_coef_planes(comp, g, g.world, coef, p);
-  const int ntiles = p.nT * g.world * p.nT;
+// One side's coefficient block of x's slots by the G step gs into coef: planes of n_pad rows,
+// x.nq * n_pad columns. block: the kBlock form (the one slot's columns are x.zcol's rows), which a G
+// step that indexes the gathered buffers does not have. bias_part: see XvCoefParams.
+template <class GStep>
+void xv_launch_coef(DType comp, const dev::XvParams& x, const GStep& gs, const Geometry& g, int side, void* coef,
+                    float* bias_part, bool block, hipStream_t stream) {
+  constexpr bool kHasBlock = GStep::kBlockForm;
+  NTXENT_CHECK(kHasBlock || !block, "xview coefficient pass: this loss has no block form");
+  dev::XvCoefParams<GStep> pc{x, gs};
+  pc.side = side;
+  pc.gbuf = static_cast<char*>(coef);
+  pc.ldg = (long long)x.nq * xv_npad(g) * (long long)dtype_size(comp);
+  pc.plane_bytes = (long long)xv_npad(g) * pc.ldg;
+  pc.bias_part = bias_part;
+  const dim3 grid(x.nT * x.nq * x.nT);
   dispatch_comp(comp, [&](auto tc) {
-    hipLaunchKernelGGL((dev::xview_side_coef_kernel<decltype(tc)>), dim3(ntiles), dim3(dev::kXvThreads), 0, stream, p);
+    dispatch_flag(kHasBlock && block, [&](auto blk) {
+      constexpr bool kBlock = kHasBlock && decltype(blk)::value;
+      hipLaunchKernelGGL((dev::xview_side_coef_kernel<decltype(tc), GStep, kBlock>), grid, dim3(dev::kXvThreads), 0,
+                         stream, pc);
+    });
   });
 }
 
@@ -1045,7 +1058,7 @@ void launch_xview_coef(DType comp, const void* zq, const float* lse2, const floa
   NTXENT_CHECK(zq && lse2 && cpos && coef && zt, "xview_coef: null buffer");
   const dev::XvParams p = xv_params_one(comp, zq, g, "xview_coef");
   xv_launch_zt(comp, zq, g, g.world, zt, stream);
-  xv_launch_coef(comp, p, g, 0, lse2, cpos, coef, stream);
+  xv_launch_coef(comp, p, dev::XvInfoNceG{lse2, cpos}, g, 0, coef, nullptr, false, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -1098,10 +1111,9 @@ size_t xview_fused_dz_bytes(const Geometry& g, int col_splits) {
 void launch_xview_fused_bwd(DType comp, const void* zq_all, const float* lse2_all, const float* cpos, const Geometry& g,
                             const void* zt, float* dz, int col_splits, hipStream_t stream) {
   NTXENT_CHECK(zq_all && lse2_all && cpos && zt && dz, "xview_fused_bwd: null buffer");
-  dev::XvFuseParams pf{};
+  dev::XvFuseParams<dev::XvInfoNceG> pf{};
   pf.x = xv_params(comp, zq_all, g, "xview_fused_bwd");
-  pf.x.lse2 = lse2_all;
-  pf.x.cpos = cpos;
+  pf.g = {lse2_all, cpos};
   const size_t es = dtype_size(comp);
   const int np = xv_npad(g), en = xv_en(g);
   NTXENT_CHECK(en <= g.dim_n && ((size_t)np * es) % kKStepBytes == 0, "xview_fused_bwd: dim_n < roundup(dim_k, 128)");
@@ -1133,9 +1145,9 @@ dev::XvSigParams xv_sig_params(DType comp, const void* zq, const void* rows_q, c
   xv_slot_range(ps.x, g, q_lo, q_hi, q_skip, who);
   NTXENT_CHECK(!rows_q || ps.x.nq == 1, who + ": a block is one slot");
   ps.x.zcol = static_cast<const char*>(rows_q);
-  ps.scale2 = (double)g.inv_temp * 1.4426950408889634;
-  ps.bias2 = (double)bias * 1.4426950408889634;
-  ps.pos_cos = rows_q && q_lo != g.rank ? nullptr : pos_cos;  // the own block alone holds positives
+  ps.g.scale2 = (double)g.inv_temp * 1.4426950408889634;
+  ps.g.bias2 = (double)bias * 1.4426950408889634;
+  ps.g.pos_cos = rows_q && q_lo != g.rank ? nullptr : pos_cos;  // the own block alone holds positives
   return ps;
 }
 // side 0's tiles of a rank: nT row tiles x world * nT column tiles
@@ -1148,28 +1160,10 @@ void xv_sig_launch_fwd(DType comp, dev::XvSigParams ps, double* lpart, bool bloc
   ps.lpart = lpart;
   const dim3 grid(ps.x.nT * ps.x.nq * ps.x.nT);
   dispatch_comp(comp, [&](auto tc) {
-    using Tc = decltype(tc);
-    if (!block) {
-      hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, ps);
-    } else {
-      hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<Tc, true>), grid, dim3(dev::kXvThreads), 0, stream, ps);
-    }
-  });
-}
-// one side's block against ps's slots into coef (xv_coef_planes); bias_part with side 0 and only there
-void xv_sig_launch_coef(DType comp, dev::XvSigParams ps, const Geometry& g, int side, void* coef, float* bias_part,
-                        bool block, hipStream_t stream) {
-  ps.x.side = side;
-  xv_coef_planes(comp, g, ps.x.nq, coef, ps.x);
-  ps.bias_part = bias_part;
-  const dim3 grid(ps.x.nT * ps.x.nq * ps.x.nT);
-  dispatch_comp(comp, [&](auto tc) {
-    using Tc = decltype(tc);
-    if (!block) {
-      hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<Tc>), grid, dim3(dev::kXvThreads), 0, stream, ps);
-    } else {
-      hipLaunchKernelGGL((dev::xview_sigmoid_coef_kernel<Tc, true>), grid, dim3(dev::kXvThreads), 0, stream, ps);
-    }
+    dispatch_flag(block, [&](auto blk) {
+      hipLaunchKernelGGL((dev::xview_sigmoid_fwd_kernel<decltype(tc), decltype(blk)::value>), grid,
+                         dim3(dev::kXvThreads), 0, stream, ps);
+    });
   });
 }
 }  // namespace
@@ -1207,7 +1201,7 @@ void launch_xview_sigmoid_coef(DType comp, const void* zq, const Geometry& g, fl
   NTXENT_CHECK(zq && coef && zt && bias_part, "xview_sigmoid_coef: null buffer");
   const dev::XvSigParams ps = xv_sig_params(comp, zq, nullptr, g, bias, 0, 1, -1, pos_cos, "xview_sigmoid_coef", true);
   xv_launch_zt(comp, zq, g, g.world, zt, stream);
-  xv_sig_launch_coef(comp, ps, g, 0, coef, bias_part, false, stream);
+  xv_launch_coef(comp, ps.x, ps.g, g, 0, coef, bias_part, false, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -1252,7 +1246,7 @@ void launch_xview_sigmoid_dist_coef(DType comp, const void* zq, const void* rows
   NTXENT_CHECK((side == 0) == (bias_part != nullptr), "xview_sigmoid_dist_coef: bias_part with side 0 and only there");
   const dev::XvSigParams ps = xv_sig_params(comp, zq, rows_q, g, bias, rows_q ? q : 0, rows_q ? q + 1 : g.world, -1,
                                             pos_cos, "xview_sigmoid_dist_coef");
-  xv_sig_launch_coef(comp, ps, g, side, coef, bias_part, rows_q != nullptr, stream);
+  xv_launch_coef(comp, ps.x, ps.g, g, side, coef, bias_part, rows_q != nullptr, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -1288,7 +1282,8 @@ void launch_xview_dist_zt(DType comp, const void* rows, const Geometry& g, int k
 void launch_xview_dist_coef(DType comp, const void* zq_all, const float* lse2_all, const float* cpos,
                             const Geometry& g, int side, void* coef, hipStream_t stream) {
   NTXENT_CHECK(zq_all && lse2_all && cpos && coef && (side == 0 || side == 1), "xview_dist_coef: bad argument");
-  xv_launch_coef(comp, xv_params(comp, zq_all, g, "xview_dist_coef"), g, side, lse2_all, cpos, coef, stream);
+  xv_launch_coef(comp, xv_params(comp, zq_all, g, "xview_dist_coef"), dev::XvInfoNceG{lse2_all, cpos}, g, side, coef,
+                 nullptr, false, stream);
   NTXENT_HIP_CHECK(hipGetLastError());
 }
 
@@ -1301,12 +1296,10 @@ void launch_xview_dist_dz(DType comp, const void* coef, const void* zt, const Ge
   q.side = side;
   const dim3 grid(q.En / dev::kXvTile, xv_npad(g) / dev::kXvTile);
   dispatch_comp(comp, [&](auto tc) {
-    using Tc = decltype(tc);
-    if (accumulate) {
-      hipLaunchKernelGGL((dev::xview_dz_kernel<Tc, true>), grid, dim3(dev::kXvThreads), 0, stream, q);
-    } else {
-      hipLaunchKernelGGL((dev::xview_dz_kernel<Tc, false>), grid, dim3(dev::kXvThreads), 0, stream, q);
-    }
+    dispatch_flag(accumulate, [&](auto acc) {
+      hipLaunchKernelGGL((dev::xview_dz_kernel<decltype(tc), decltype(acc)::value>), grid, dim3(dev::kXvThreads), 0,
+                         stream, q);
+    });
   });
   NTXENT_HIP_CHECK(hipGetLastError());
 }

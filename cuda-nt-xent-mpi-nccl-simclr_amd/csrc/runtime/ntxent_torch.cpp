@@ -386,6 +386,20 @@ static at::Tensor xview_backward_tail(const at::Tensor& h, const at::Tensor& inv
   return dh;
 }
 
+// The end of the one-GPU backward of both losses, stored or fused: xview_backward_tail over the
+// nslabs slabs, and in *dtau (null: not wanted) dL/dtau times grad_out, a 0-d fp32 tensor.
+static at::Tensor xview_backward_finish(const at::Tensor& h, const at::Tensor& inv, const at::Tensor& go,
+                                        const at::Tensor& dz, const Geometry& g, hipStream_t stream, int nslabs,
+                                        at::Tensor* dtau) {
+  at::Tensor dot;
+  auto dh = xview_backward_tail(h, inv, go, dz, g, stream, &dot, nslabs);
+  if (dtau) {
+    *dtau = at::empty({}, opts(h, at::kFloat));
+    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau->data_ptr<float>(), g, stream);
+  }
+  return dh;
+}
+
 // 16-bit plans of the pairwise sigmoid loss: the pairs' cosines from the input rows in fp32
 // (launch_xview_sigmoid_pos), [R/2]; undefined for fp32 plans. The forward and the backward form them
 // from the same h and inv: the same bits.
@@ -445,13 +459,7 @@ static at::Tensor xview_backward_body(const at::Tensor& h, const at::Tensor& inv
   launch_xview_dz(P.comp, coef.data_ptr(), zt.data_ptr(), g, dz.data_ptr<float>(), stream);
   coef.reset();
   zt.reset();
-  at::Tensor dot;
-  auto dh = xview_backward_tail(h, inv, go, dz, g, stream, &dot);
-  if (dtau) {
-    *dtau = at::empty({}, opts(h, at::kFloat));
-    launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau->data_ptr<float>(), g, stream);
-  }
-  return dh;
+  return xview_backward_finish(h, inv, go, dz, g, stream, 1, dtau);
 }
 
 // dtau as xview_backward_body's. compute: the forward's.
@@ -474,13 +482,7 @@ static at::Tensor xview_backward_impl(const at::Tensor& h, const at::Tensor& inv
       const auto st = prep(h, *P, c10::nullopt, c10::nullopt);
       dz = xview_fused_dz(*P, h, st[0].data_ptr(), lse2, cpos, col_splits, stream, &nslabs);
     }
-    at::Tensor dot;
-    auto dh = xview_backward_tail(h, inv, go, dz, P->g, stream, &dot, nslabs);
-    if (dtau) {
-      *dtau = at::empty({}, opts(h, at::kFloat));
-      launch_tau_grad(dot.data_ptr<float>(), go.data_ptr<float>(), dtau->data_ptr<float>(), P->g, stream);
-    }
-    return dh;
+    return xview_backward_finish(h, inv, go, dz, P->g, stream, nslabs, dtau);
   }
   return xview_backward_body(h, inv, grad_scalar(grad_out), *P, nullptr, dtau,
                              [&](void* zq, void* coef, void* zt, const float*, hipStream_t stream) {

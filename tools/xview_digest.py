@@ -9,6 +9,8 @@ with a CPU torch.Generator, in a fixed order:
   info_nce   loss, dh, dL/dtau of ``info_nce_loss`` (tau = 0.07 as a tensor that requires grad)
   pos_rank   rank, pos_cos, hard_neg_cos of ``positive_rank``
   xview_dist loss and every rank's dh of ``emulated_xview_forward_backward``
+  info_nce_fused, xview_dist_fused  the same two with ``backward="fused"``
+             (a build without the fused backward prints none of these lines)
   sigmoid    loss, dh, dL/dtau, dL/dbias of ``sigmoid_loss`` (tau = 0.1, bias = -10 as tensors that require grad)
   sigmoid_dist loss, dL/dtau, dL/dbias and every rank's dh of ``emulated_sigmoid_forward_backward``
              (a build without the distributed sigmoid loss prints none of these lines)
@@ -53,21 +55,29 @@ def main():
 
     print(f"# build {_ext.load(build_if_missing=False).__file__}")
     dev = torch.device("cuda", 0)
+
+    def backwards(fn, name):
+        """The stored backward under the plain name, then the fused one where the build has it."""
+        fused = "backward" in inspect.signature(fn).parameters
+        return [(name, {})] + ([(name + "_fused", {"backward": "fused"})] if fused else [])
+
     for n, d in ONE_GPU:
         h = rows(n, d, 1000 * n + d).to(dev)
         for comp in COMPUTES:
-            x = h.clone().requires_grad_(True)
-            tau = torch.tensor(TAU, device=dev, requires_grad=True)
-            loss = ntxent_amd.info_nce_loss(x, tau, compute=comp)
-            dh, dtau = torch.autograd.grad(loss, (x, tau))
-            print(f"info_nce N={n} d={d} {comp}: loss {digest(loss)} dh {digest(dh)} dtau {digest(dtau)}")
+            for name, kw in backwards(ntxent_amd.info_nce_loss, "info_nce"):
+                x = h.clone().requires_grad_(True)
+                tau = torch.tensor(TAU, device=dev, requires_grad=True)
+                loss = ntxent_amd.info_nce_loss(x, tau, compute=comp, **kw)
+                dh, dtau = torch.autograd.grad(loss, (x, tau))
+                print(f"{name} N={n} d={d} {comp}: loss {digest(loss)} dh {digest(dh)} dtau {digest(dtau)}")
             rank, pos, hard = ntxent_amd.positive_rank(h, compute=comp)
             print(f"pos_rank N={n} d={d} {comp}: rank {digest(rank)} pos_cos {digest(pos)} hard_neg_cos {digest(hard)}")
-    for W, n, d, comp in DIST:
-        shards = [rows(n, d, 1000 * n + d + 101 * r).to(dev) for r in range(W)]
-        loss, grads = emulated_xview_forward_backward(shards, TAU, compute=comp, grad_out=0.7)
-        print(f"xview_dist W={W} n={n} d={d} {comp}: loss {digest(loss)} " +
-              " ".join(f"dh{r} {digest(g)}" for r, g in enumerate(grads)))
+    for name, kw in backwards(emulated_xview_forward_backward, "xview_dist"):
+        for W, n, d, comp in DIST:
+            shards = [rows(n, d, 1000 * n + d + 101 * r).to(dev) for r in range(W)]
+            loss, grads = emulated_xview_forward_backward(shards, TAU, compute=comp, grad_out=0.7, **kw)
+            print(f"{name} W={W} n={n} d={d} {comp}: loss {digest(loss)} " +
+                  " ".join(f"dh{r} {digest(g)}" for r, g in enumerate(grads)))
     for n, d in ONE_GPU:
         h = rows(n, d, 1000 * n + d).to(dev)
         for comp in COMPUTES:
